@@ -14,11 +14,13 @@ Inputs (transition table, trace) and outputs (verdicts) are resident in HBM duri
 
 Every timed step evaluates FRESH seeds: step i of rank r runs the schedule indices [(i * W + r) * n, ... + n), so that
 `bugs_per_hr` counts the distinct violating executions (by the 64-bit hash over every delivered message and every final
-state) found in the timed region per wall-clock hour; one more, untimed, step on the fixed indices [r * n, ...) follows for the
-bit-for-bit comparison with the CPU oracle.
+state) found in the timed region per wall-clock hour.  `--dump-outputs DIR` writes the last timed step's verdicts and
+found-violation set under DIR (the seeds make them the same from run to run).
 
-The one JSON line also carries, under "secondary" (after the timed region), the other loops of the hot path on their BASELINE
-configurations, each with its own roofline and CPU baseline:
+A plain run does only what the headline figure needs: set-up, warm-up, the timed steps, the line.  `--full` adds the same
+launches one at a time before the timed region and, after it, one more untimed step on the fixed indices [r * n, ...) for the
+bit-for-bit comparison with the CPU oracle, the device probe, the host-buffer entry points, the CPU baselines and, under
+"secondary", the other loops of the hot path on their BASELINE configurations, each with its own roofline and CPU baseline:
   config1  raft3, 100 schedules per call through host buffers (N = 1 only);
   dpor     config 3: DPORwHeuristics, raft5, depth 30 — the whole bounded exploration (interleavings/s), in ROUNDS order and
            in the reference's own order (N = 1 only: the reference order's commit is one sequential loop);
@@ -50,6 +52,7 @@ N_PER_GPU = 1 << 20           # "1M random interleavings on 1 MI355X"
 VIOL_CAP = 1 << 16            # found-violation list capacity per rank and step
 HBM_PEAK_GBS = 8000.0         # MI355X_MICROARCH.md: HBM3E 8 TB/s spec peak
 PREWARM_S = 1.5               # untimed launches before the warmup steps: the shader clock ramps over ~1 s (DVFS)
+DUMP_MAX_VERDICTS = 1 << 20   # --dump-outputs: 5 x 8 MB of verdict fields, the found-violation sets beside them: under 64 MB
 K1_COUNTERS = os.path.join(ROOT, "profiles", "k1_counters.json")   # rocprofv3 --pmc passes of this workload (tools/profile_r5.sh)
 
 
@@ -946,6 +949,25 @@ def bench_ddmin(ctx_device, cpu_baseline=True, n=1 << 20):
     return out
 
 
+def dump_outputs(out_dir, verdicts, index_base, vset):
+    """--dump-outputs: what the last timed step handed its caller, one float64 .npy file per field (exact: every field fits in
+    53 bits once the 64-bit delivery hash is split into its halves).  The verdicts of at most DUMP_MAX_VERDICTS schedules (all of
+    them up to that size, else a sample drawn with a fixed seed; verdict_index names them) and the found-violation set."""
+    import numpy as np
+    from demi_amd import types as T
+    v = verdicts.view(T.VERDICT_DTYPE).reshape(-1)
+    idx = np.arange(len(v), dtype=np.uint64)
+    if len(v) > DUMP_MAX_VERDICTS:
+        idx = np.sort(np.random.default_rng(0).choice(len(v), DUMP_MAX_VERDICTS, replace=False)).astype(np.uint64)
+        v = v[idx]
+    arrays = {"verdict_index": idx + np.uint64(index_base), "verdict_flags": v["flags"], "verdict_fingerprint": v["fingerprint"],
+              "verdict_hash_hi": v["hash"] >> np.uint64(32), "verdict_hash_lo": v["hash"] & np.uint64(0xFFFFFFFF),
+              "violation_index": vset["index"], "violation_fingerprint": vset["fingerprint"], "violation_flags": vset["flags"]}
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a.astype(np.float64))
+
+
 def _self_launch(n_gpus):
     """Re-run this command as `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1
     --master-port P bench.py <same arguments>`; returns the launcher's exit code."""
@@ -992,9 +1014,18 @@ def main():
                          "prevLogIndex, prevLogTerm, entry, leaderCommit), RequestVote(term, candidateId, lastLogTerm, lastLogIndex))")
     ap.add_argument("--strategy", choices=["random", "fifo"], default="random",
                     help="RandomizationStrategy: FullyRandom (the headline workload) or SrcDstFIFO")
+    ap.add_argument("--full", action="store_true",
+                    help="fuzz: also the measurements and checks beyond the headline figure (one launch at a time, the fixed-seed "
+                         "step against the CPU oracle, device probe, host-buffer entry points, CPU baselines, the secondary records)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="fuzz: write what the last timed step computed (its verdicts and found-violation set) as DIR/<name>.npy")
     args = ap.parse_args()
     if args.real_fields and not args.log_cap:
         ap.error("--real-fields needs --log-cap N (the field sets include the log's prevLogIndex / prevLogTerm / entry)")
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.workload != "fuzz":
+        ap.error("--dump-outputs writes the fuzz workload's outputs (--workload fuzz)")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` without a launcher: become the launcher.  One rank per GPU under torch.distributed.run
@@ -1207,7 +1238,7 @@ def main():
     # launches one at a time (one context, one stream), untimed and BEFORE the timed region: what a launch takes with the
     # device to itself - the duration the committed counters and the issue model below belong to
     alone = None
-    if n_lanes == 2:
+    if n_lanes == 2 and args.full:
         ea = [torch.cuda.Event(enable_timing=True) for _ in range(2 * args.steps)]
         l0 = lanes[0]
         ta = time.perf_counter()
@@ -1240,6 +1271,12 @@ def main():
         dt = float(t.item())
     kernel_ms = float(np.mean([a.elapsed_time(b) for a, b in zip(ev0, ev1)]))
     kernel_ms_alone = alone["kernel_ms"] if alone else kernel_ms
+    from demi_amd.distributed import merge_violation_sets
+    if args.dump_outputs and rank == 0:
+        last = lanes[(args.steps - 1) % n_lanes]
+        vparts = [last.gathered[r] for r in range(world)] if world > 1 else [last.viol]
+        dump_outputs(args.dump_outputs, vbuf[(args.steps - 1) % keep_steps].cpu().numpy(), ((args.steps - 1) * world + rank) * n,
+                     merge_violation_sets([p.cpu().numpy() for p in vparts], VIOL_CAP))
 
     # ---- what the timed region found: the violating executions of its steps, by delivery-sequence hash and by fingerprint
     # (bugs/hr = distinct violating schedules per wall-clock hour); counted here, after the timed region
@@ -1254,13 +1291,13 @@ def main():
     timed_fps = int(len(np.unique(np.concatenate([p[2] for p in parts])))) if parts else 0
     counted_frac = keep_steps / float(args.steps)
 
-    # ---- one more, untimed, step on the fixed indices [r * n, ...): the found-violation set every rank ends up with, and the
-    # verdicts the CPU oracle is compared with bit for bit
-    from demi_amd.distributed import merge_violation_sets
-    step()
-    sync()
-    vparts = [gathered[r] for r in range(world)] if world > 1 else [viol]
-    vset = merge_violation_sets([p.cpu().numpy() for p in vparts], VIOL_CAP)
+    # ---- (--full) one more, untimed, step on the fixed indices [r * n, ...): the found-violation set every rank ends up with,
+    # and the verdicts the CPU oracle is compared with bit for bit
+    if args.full:
+        step()
+        sync()
+        vparts = [gathered[r] for r in range(world)] if world > 1 else [viol]
+        vset = merge_violation_sets([p.cpu().numpy() for p in vparts], VIOL_CAP)
     index_base = rank * n
 
     out = None
@@ -1273,20 +1310,21 @@ def main():
                      ((3 if specialized else 2) if args.strategy == "fifo" else 4 if getattr(model, "wide", False) else (6 if specialized else 3)))
         shared = 8 * len(events) + 4 * len(model.code) + 4 * len(model.handler_start) + 8 * 8 + 32 * 4 + 132 * 4 + 64 * 4
         alg_bytes = 16 * n + blocks * shared
-        # measured on this box, right after the timed region: the shader clock under load and the SIMD cycles per wave64
-        # integer VALU instruction (alone on the SIMD / with 6 waves competing as in K1)
+        # (--full) measured in this run, right after the timed region: the shader clock under load and the SIMD cycles per
+        # wave64 integer VALU instruction (alone on the SIMD / with 6 waves competing as in K1)
         probe = None
         try:
-            p1, p6 = ctx.device_probe(1, 20000), ctx.device_probe(6, 6000)
-            s6, m6, d6 = ctx.device_probe(6, 6000, 1), ctx.device_probe(6, 6000, 2), ctx.device_probe(6, 6000, 3)
-            probe = {"shader_clock_ghz": p6.shader_clock_ghz, "simd_cycles_per_int_valu_1_wave": p1.cycles_per_valu,
-                     "simd_cycles_per_int_valu_6_waves": p6.cycles_per_valu,
-                     "simd_cycles_per_salu_6_waves": s6.cycles_per_valu,
-                     "simd_cycles_per_inst_valu_salu_alternating_6_waves": m6.cycles_per_valu,
-                     "simd_cycles_per_inst_divergent_if_6_waves": d6.cycles_per_valu,
-                     "how": "demi_device_probe_mix: s_memtime cycles per 100 MHz wall_clock64 tick; unrolled passes of "
-                            "independent integer VALU instructions / SALU instructions / the two alternating / the code of a "
-                            "divergent two-instruction if, with 6 waves per SIMD as in K1"}
+            if args.full:
+                p1, p6 = ctx.device_probe(1, 20000), ctx.device_probe(6, 6000)
+                s6, m6, d6 = ctx.device_probe(6, 6000, 1), ctx.device_probe(6, 6000, 2), ctx.device_probe(6, 6000, 3)
+                probe = {"shader_clock_ghz": p6.shader_clock_ghz, "simd_cycles_per_int_valu_1_wave": p1.cycles_per_valu,
+                         "simd_cycles_per_int_valu_6_waves": p6.cycles_per_valu,
+                         "simd_cycles_per_salu_6_waves": s6.cycles_per_valu,
+                         "simd_cycles_per_inst_valu_salu_alternating_6_waves": m6.cycles_per_valu,
+                         "simd_cycles_per_inst_divergent_if_6_waves": d6.cycles_per_valu,
+                         "how": "demi_device_probe_mix: s_memtime cycles per 100 MHz wall_clock64 tick; unrolled passes of "
+                                "independent integer VALU instructions / SALU instructions / the two alternating / the code of a "
+                                "divergent two-instruction if, with 6 waves per SIMD as in K1"}
         except Exception as e:
             print("bench: device probe failed: %s" % e, file=sys.stderr)
         # rocprofv3 counters of THIS kernel build on this workload (tools/profile_r4.sh writes profiles/k1_counters.json with
@@ -1346,8 +1384,6 @@ def main():
                              "k1_launches_before": k1_launches_before, "k1_launches": args.steps,
                              "distinct_violating_delivery_hashes": timed_hashes, "distinct_fingerprints": timed_fps,
                              "steps_counted": keep_steps},
-            "violations_last_step": int(len(vset)),
-            "distinct_fingerprints_last_step": int(len(np.unique(vset["fingerprint"]))) if len(vset) else 0,
             "roofline": roofline(alg_bytes, kernel_ms, traffic,
                                  ("k1_random_explore<false, true>" if args.strategy == "fifo" else "k1_random_explore<false, false>") +
                                  (" (specialised, hiprtc)" if specialized else ""),
@@ -1365,7 +1401,10 @@ def main():
         }
         if alone:
             out["one_launch_at_a_time"] = alone
-        if world == 1:
+        if args.full:
+            out["violations_last_step"] = int(len(vset))
+            out["distinct_fingerprints_last_step"] = int(len(np.unique(vset["fingerprint"]))) if len(vset) else 0
+        if world == 1 and args.full:
             # what a JVM host sees through demi_random_explore (caller's pageable host buffer for the verdicts): the same
             # launch plus the copy over PCIe.  Never `value` (inputs / outputs resident in HBM); reported beside it.
             try:
@@ -1414,7 +1453,7 @@ def main():
                                                    "violating_executions_returned": int(nf)}}
             except Exception as e:           # never let a side measurement break the bench line
                 print("bench: host-buffer measurement unavailable: %s" % e, file=sys.stderr)
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             from oracle import oracle_py as O
             cores = os.cpu_count() or 1
             m = min(args.cpu_sample, n)
@@ -1439,7 +1478,7 @@ def main():
         c.close()
     del vbuf
     torch.cuda.empty_cache()
-    if not args.no_secondary:
+    if args.full and not args.no_secondary:
         sec = {}
         if world == 1:
             for name, fn in (("config1", bench_config1), ("dpor", bench_dpor), ("ddmin", bench_ddmin), ("more_than_8_actors", bench_big_tables),

@@ -148,7 +148,7 @@ def test_bench_py_two_ranks_on_one_gpu(tmp_path):
     env = dict(os.environ, DEMI_BENCH_BACKEND="gloo", DEMI_BENCH_ONE_GPU="1", DEMI_BENCH_COMM="host")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", "29547", os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-           "--schedules", "65536", "--no-prewarm", "--config5-budget", "40000"]
+           "--schedules", "65536", "--no-prewarm", "--config5-budget", "40000", "--full"]
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=1500)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -173,7 +173,7 @@ def test_bench_py_two_ranks_on_one_gpu(tmp_path):
     assert c5["n_gpus"] == 2 and c5["interleavings"] == 40000 and not c5["exhausted"] and c5["same_verdict_sequence_on_every_rank"]
     # both ranks' violations are in the merged set: rank 1 evaluates the indices [65536, 131072)
     one = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "1", "--warmup", "0", "--schedules", "65536",
-                          "--no-prewarm", "--no-cpu-baseline", "--no-secondary"], capture_output=True, text=True, timeout=600)
+                          "--no-prewarm", "--no-cpu-baseline", "--no-secondary", "--full"], capture_output=True, text=True, timeout=600)
     d1 = json.loads([l for l in one.stdout.splitlines() if l.startswith("{")][0])
     assert d["violations_last_step"] > d1["violations_last_step"] > 0
 

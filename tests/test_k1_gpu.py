@@ -637,3 +637,34 @@ def test_explore_in_calls_is_explore_in_one_call(oracle):
     s2.chunk = 1024
     assert s2.explore(events) is None and s2.last_calls == 5
     s2.shutdown()
+
+
+def test_bench_py_plain_line_and_dumped_outputs(tmp_path, oracle):
+    """A plain `bench.py` run: the headline fields, exactly --steps timed steps, none of what --full adds; --dump-outputs
+    writes the last timed step's verdicts and found-violation set, which are the CPU oracle's for the same schedule indices."""
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    n, steps = 65536, 3
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", str(steps), "--warmup", "1", "--schedules", str(n),
+                          "--no-prewarm", "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-3000:]
+    lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, out.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert all(k in d for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"))
+    assert d["steps"] == steps and d["timed_region"]["k1_launches"] == steps and d["timed_region"]["schedules"] == steps * n
+    assert d["value"] > 0 and d["ms_per_step"] > 0
+    assert not any(k in d for k in ("secondary", "cpu_baseline", "pcie_inclusive", "one_launch_at_a_time", "violations_last_step"))
+    got = {f[:-4]: np.load(str(tmp_path / f)) for f in os.listdir(str(tmp_path))}
+    assert all(a.dtype == np.float64 for a in got.values())
+    base = (steps - 1) * n                          # timed step i runs the schedule indices [i * n, (i + 1) * n)
+    assert (got["verdict_index"] == base + np.arange(n)).all()
+    model, events, lim = raft5_config2()
+    want = oracle.random_explore(model, events, n, seed_base=SEED_BASE + base, limits=lim, n_threads=os.cpu_count())
+    assert (got["verdict_flags"] == want["flags"]).all() and (got["verdict_fingerprint"] == want["fingerprint"]).all()
+    assert (got["verdict_hash_hi"] == want["hash"] >> np.uint64(32)).all()
+    assert (got["verdict_hash_lo"] == want["hash"] & np.uint64(0xFFFFFFFF)).all()
+    viol = np.nonzero(want["flags"] & T.V_VIOLATION)[0]
+    assert len(viol) and (got["violation_index"] == base + viol).all()
+    assert (got["violation_fingerprint"] == want["fingerprint"][viol]).all() and (got["violation_flags"] == want["flags"][viol]).all()

@@ -1,4 +1,4 @@
-"""Prints the records of a bench line (python bench.py > file) as the markdown table DESIGN.md section 5 carries per round:
+"""Prints the records of a bench line (python bench.py --full > file) as the markdown table DESIGN.md section 5 carries per round:
    python tools/bench_table.py profiles/r06_bench_1gpu.json"""
 import json
 import sys
