@@ -17,7 +17,8 @@ EXPORTS = ["demi_ctx_create", "demi_ctx_destroy", "demi_last_error", "demi_versi
            "demi_replay_removal_batch", "demi_replay_get_kept", "demi_replay_recorded_len", "demi_ddmin", "demi_dpor_set_traces", "demi_model_specialize", "demi_model_is_specialized", "demi_model_code_id",
            "demi_specialize_check", "demi_specialize_source", "demi_specialize_source_k1", "demi_provenance_prune", "demi_device_probe", "demi_device_probe_mix", "demi_calib_rw", "demi_random_explore_flagged", "demi_collect_flagged_dev", "demi_random_explore_submit", "demi_random_explore_wait", "demi_trace_len",
            "demi_comm_unique_id", "demi_comm_create", "demi_comm_create_host", "demi_comm_destroy", "demi_comm_rank",
-           "demi_comm_allgather_dev", "demi_random_explore_sharded", "demi_replay_batch_sharded", "demi_abi_version", "demi_replay_externals_len", "demi_edit_distance_dpor_ddmin", "demi_dpor_explored", "demi_random_ddmin", "demi_random_explore_candidates", "demi_ext_payload_areas"]
+           "demi_comm_allgather_dev", "demi_random_explore_sharded", "demi_replay_batch_sharded", "demi_abi_version", "demi_replay_externals_len", "demi_edit_distance_dpor_ddmin", "demi_dpor_explored", "demi_random_ddmin", "demi_random_explore_candidates", "demi_ext_payload_areas",
+           "demi_replay_wildcard_load", "demi_replay_wildcard_batch", "demi_replay_wildcard_get_trace"]
 
 _lib = None
 ALLGATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t)     # demi_allgather_fn
@@ -96,6 +97,10 @@ def lib():
     L.demi_replay_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(T.Limits), C.c_void_p]
     L.demi_replay_batch_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(T.Limits), C.c_void_p, C.c_void_p]
     L.demi_replay_removal_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(T.Limits), C.c_void_p]
+    L.demi_replay_wildcard_load.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    L.demi_replay_wildcard_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(T.Limits), C.c_void_p]
+    L.demi_replay_wildcard_get_trace.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(T.Limits), C.POINTER(T.Verdict),
+                                                 C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]
     L.demi_replay_get_kept.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(T.Limits), C.POINTER(T.Verdict),
                                        C.c_void_p]
     L.demi_dpor_load.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
@@ -366,6 +371,69 @@ class Context:
         self._check(lib().demi_replay_get_kept(self._h, mp, C.c_uint32(int(skip) & 0xFFFFFFFF), C.byref(limits),
                                                C.byref(v), kept.ctypes.data))
         return v, kept[:int(n_rec)]
+
+    def replay_wildcard_load(self, type_sets, policies):
+        """The selector of every recorded event of the loaded execution (demi_replay_wildcard_load): type_sets uint32[n_rec]
+        (0 = exact delivery), policies uint8[n_rec] (types.WILDCARD_HEAD / FIRST / LAST)."""
+        import numpy as np
+        ts = np.ascontiguousarray(type_sets, dtype=np.uint32)
+        po = np.ascontiguousarray(policies, dtype=np.uint8)
+        n_rec = int(lib().demi_replay_recorded_len(self._h))
+        if len(ts) != n_rec or len(po) != n_rec:
+            raise ValueError("one selector per recorded event of the loaded trace")
+        pad = np.zeros(1, dtype=np.uint32)
+        self._check(lib().demi_replay_wildcard_load(self._h, (ts if n_rec else pad).ctypes.data,
+                                                    (po if n_rec else pad.view(np.uint8)).ctypes.data))
+
+    @staticmethod
+    def _present_words(present, n_rec):
+        """bool[n, n_rec] (or already packed uint64[n, words]) -> uint64[n, ceil(n_rec / 64)]."""
+        import numpy as np
+        present = np.asarray(present)
+        words = (int(n_rec) + 63) // 64
+        if present.dtype == np.uint64:
+            return np.ascontiguousarray(present).reshape(-1, max(words, 1))[:, :words] if words else present.reshape(len(present), 0)
+        present = present.reshape(-1, int(n_rec)).astype(bool)
+        padded = np.zeros((len(present), words * 64), dtype=np.uint8)
+        padded[:, :int(n_rec)] = present
+        return np.ascontiguousarray(np.packbits(padded, axis=1, bitorder="little")).view(np.uint64).reshape(len(present), words)
+
+    def replay_wildcard_batch(self, present, limits, masks=None):
+        """One STSScheduler.test per row of `present` (bool[n, n_rec]: which recorded MsgEvents the candidate's trace holds)."""
+        import numpy as np
+        n_rec = int(lib().demi_replay_recorded_len(self._h))
+        pw = self._present_words(present, n_rec)
+        out = np.zeros(len(pw), dtype=T.VERDICT_DTYPE)
+        if len(pw) == 0:
+            return out
+        mp = None
+        if masks is not None:
+            masks = np.ascontiguousarray(masks, dtype=np.uint64).reshape(-1, 4)
+            if len(masks) != len(pw):
+                raise ValueError("one mask per candidate")
+            mp = masks.ctypes.data
+        self._check(lib().demi_replay_wildcard_batch(self._h, mp, pw.ctypes.data if pw.size else out.ctypes.data, len(pw),
+                                                     C.byref(limits), out.ctypes.data))
+        return out
+
+    def replay_wildcard_get_trace(self, present, limits, mask=None, cap=None):
+        """(Verdict, kept uint8[n_rec], executed trace as REC_EVENT records) of one candidate (demi_replay_wildcard_get_trace)."""
+        import numpy as np
+        n_rec = int(lib().demi_replay_recorded_len(self._h))
+        pw = self._present_words(np.asarray(present).reshape(1, -1), n_rec)
+        mp = None
+        if mask is not None:
+            mask = np.ascontiguousarray(mask, dtype=np.uint64).reshape(4)
+            mp = mask.ctypes.data
+        cap = int(cap) if cap is not None else T.MAX_REC_EVENTS
+        v = T.Verdict()
+        kept = np.zeros(max(n_rec, 1), dtype=np.uint8)
+        rec = np.zeros(max(cap, 1), dtype=T.REC_EVENT_DTYPE)
+        n_out = C.c_uint32(0)
+        dummy = np.zeros(1, dtype=np.uint64)
+        self._check(lib().demi_replay_wildcard_get_trace(self._h, mp, (pw if pw.size else dummy).ctypes.data, C.byref(limits),
+                                                         C.byref(v), kept.ctypes.data, rec.ctypes.data, cap, C.byref(n_out)))
+        return v, kept[:n_rec], rec[:n_out.value].copy()
 
     def dpor_load(self, externals, areas=None):
         import numpy as np

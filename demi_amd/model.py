@@ -247,6 +247,11 @@ class Model:
     wide: bool = False                # DEMI_MODEL_WIDE: 16 x u16 register window
     array_len: int = 0                # DEMI_MODEL_ARRAY: elements of every actor's array (LDX / STX), 0 = none
     payloads: int = 2                 # DEMI_MODEL_PAYLOADS: payload fields per message (3..6 need a wide table)
+    # The logical-clock hooks of MessageFingerprinter (MessageFingerprints.scala:26-31), host-side metadata of the wildcard
+    # minimizers only (wildcard_minimization.py; the device never sees them): causesClockIncrement = the message's type is in
+    # clock_increment_types; getLogicalClock = payload field clock_field[type] of a message whose type has an entry, else None
+    clock_increment_types: frozenset = field(default=frozenset(), compare=False)
+    clock_field: dict = field(default_factory=dict, compare=False)
     _keep: list = field(default_factory=list, repr=False, compare=False)
 
     @property
@@ -563,11 +568,15 @@ def raft_model(n_actors=5, election_budget=1, buggy=True, term0=0, loglen0=0, in
     budgets = list(election_budget) if isinstance(election_budget, (list, tuple)) else [election_budget] * n_actors
     assert len(budgets) == n_actors
     init = [[FOLLOWER, term0, NOBODY, 0, b, loglen0, loglen0, 0] for b in budgets]
-    return build_model("raft%d-synth%s%s%s%s%s" % (n_actors, "" if buggy else "-fixed", "-wide" if wide else "", "-log%d" % log_cap if log_cap else "",
+    model = build_model("raft%d-synth%s%s%s%s%s" % (n_actors, "" if buggy else "-fixed", "-wide" if wide else "", "-log%d" % log_cap if log_cap else "",
                                                    "-fields" if real_fields else "",
                                                    "-eb" + "".join(str(b) for b in budgets) if len(set(budgets)) > 1 else ""),
                        n_actors, RAFT_MSGS, h, init, invariant=invariant or (T.INV_AT_MOST_ONE, int(ROLE), LEADER, int(TERM)), wide=wide,
                        array_len=log_cap, payloads=5 if real_fields else 2)
+    # fungible clocks: the term travels in P0 of the four protocol messages; an ElectionTimeout is what bumps it
+    model.clock_increment_types = frozenset([M_ELECTION_TIMEOUT])
+    model.clock_field = {M_REQUEST_VOTE: 0, M_VOTE_REPLY: 0, M_APPEND_ENTRIES: 0, M_APPEND_REPLY: 0}
+    return model
 
 
 def save_model(model: Model, path: str):

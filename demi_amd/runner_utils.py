@@ -80,7 +80,8 @@ def fuzz(generateFuzzTest: Callable[[int], np.ndarray], schedulerConfig: Schedul
 def run_the_gamut(schedulerConfig: SchedulerConfig, trace: EventTrace, violation: ViolationFingerprint,
                   stages: Sequence[str] = ("DDMin", "IntMin"), device: int = 0, p_max: int = 64):
     """The stages of RunnerUtils.runTheGamut (:165-380) that run on the GPU path, in the reference's order:
-    stsSchedDDMin (external events), then minimizeInternals with LeftToRightOneAtATime.  Returns a dict with the MCS
+    stsSchedDDMin (external events), then minimizeInternals with LeftToRightOneAtATime, then - only when named in `stages` -
+    "WildcardsNoBackTracks" and "WildcardsLastOnly" (wildcard_minimization.WildcardMinimizer, ClockClusterizer).  Returns a dict with the MCS
     (indices into trace.original_externals), the verified MCS execution, the internally minimized execution and the
     replay counts of each stage."""
     from .internal_minimization import countMsgEvents, minimizeInternals
@@ -104,4 +105,16 @@ def run_the_gamut(schedulerConfig: SchedulerConfig, trace: EventTrace, violation
         _, minimized = minimizeInternals(schedulerConfig, cur_trace.original_externals, cur_trace, violation, stats=stats,
                                          device=device, p_max=p_max)
         out.update(intmin_replays=stats.total_replays, minimized=minimized, minimized_deliveries=countMsgEvents(minimized))
+        cur_trace = minimized
+    # the wildcard (fungible-clock) stages, opt-in, as RunnerUtils.scala:412-440 configures them: STSSched as the oracle, the
+    # default resolution strategy (BackTrackStrategy, its backtrack points no-ops) and then LastOnlyStrategy
+    for stage, strategy in (("WildcardsNoBackTracks", None), ("WildcardsLastOnly", "LastOnlyStrategy")):
+        if stage in stages and cur_trace is not None:
+            from . import wildcard_minimization as W
+            stats = MinimizationStats()
+            _, cur_trace = W.WildcardMinimizer(schedulerConfig, cur_trace.original_externals, cur_trace, violation, stats=stats,
+                                               resolutionStrategy=getattr(W, strategy)() if strategy else None,
+                                               device=device, p_max=p_max).minimize()
+            out.setdefault("wildcard_replays", {})[stage] = stats.total_replays
+            out.update(wildcard_minimized=cur_trace, wildcard_deliveries=countMsgEvents(cur_trace))
     return out

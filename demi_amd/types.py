@@ -134,6 +134,7 @@ def rec_area(e):
 
 
 FILTER_ABSENTS_OFF, FILTER_ABSENTS_LITERAL, FILTER_ABSENTS_CORRECTED = 0, 1, 2     # demi_filter_absents
+WILDCARD_HEAD, WILDCARD_FIRST, WILDCARD_LAST = 0, 1, 2     # demi_wildcard_policy
 
 
 class Limits(C.Structure):

@@ -1,0 +1,475 @@
+"""Wildcard (fungible-clock) internal minimization: which deliveries can go once the others only have to match by type.
+
+Host-side mirror of minification/wildcard_minimization/{AmbiguityResolutionStrategies, Clusterizer, OneAtATimeClusterizer,
+ClockClusterizer, WildcardMinimizer}.scala with TestScheduler.STSSched (backtrack setters are no-ops).  A Clusterizer proposes
+traces over the SAME original trace: deliveries of external messages stay exact, every other kept delivery becomes
+MsgEvent(snd, rcv, WildCardMatch(selector)), a delivery outside the current cluster is dropped (its MsgSend stays).  On the
+device (demi_replay_wildcard_*, csrc/k2_wildcard.hpp) a selector is (set of message types, policy HEAD / FIRST / LAST) and a
+proposal is a presence bitmask over the recorded events, so one load serves a whole doMinimize.  The replays are launches:
+the clusterizer is cloned, its upcoming proposals are enumerated assuming each fails, evaluated together, and consumed up to
+the first that still triggers the violation - exactly the sequence WildcardMinimizer.doMinimize walks one replay at a time
+(max_batch = 1 is that loop; every batch size gives the same result and the same stats.total_replays).
+
+A delivery's id is the Uniq id of its UniqueMsgEvent (the `id` of the record); `sorted` sequences are sorted by it, as in the
+Scala.  BeginUnignorableEvents blocks do not exist in the recorded format.  The logical-clock hooks of MessageFingerprinter are
+the model's clock_increment_types / clock_field (model.py); a model without them makes ClockClusterizer degenerate as the
+default fingerprinter does in the reference (no clock clusters, no timers).
+"""
+from typing import Dict, FrozenSet, List, Optional, Sequence, Set, Tuple
+
+import numpy as np
+
+from . import _native
+from . import types as T
+from .internal_minimization import countMsgEvents
+from .model import Model
+from .schedulers import EventTrace, MinimizationStats, SchedulerConfig, ViolationFingerprint
+
+
+# ------------------------------------------------------------------ AmbiguityResolutionStrategies.scala
+class AmbiguityResolutionStrategy:
+    """resolve(msgSelector, pending, backtrackSetter) -> index of the selected pending message, or None.  `policy` is what the
+    device knows the strategy as."""
+    policy = T.WILDCARD_FIRST
+
+    def resolve(self, msgSelector, pending: Sequence, backtrackSetter=None) -> Optional[int]:
+        matching = [i for i, m in enumerate(pending) if msgSelector(m)]
+        return matching[0] if matching else None
+
+
+class SrcDstFIFOOnly(AmbiguityResolutionStrategy):
+    """:18-34: if the first pending message doesn't match, give up."""
+    policy = T.WILDCARD_HEAD
+
+    def resolve(self, msgSelector, pending, backtrackSetter=None):
+        return 0 if len(pending) and msgSelector(pending[0]) else None
+
+
+class BackTrackStrategy(AmbiguityResolutionStrategy):
+    """:45-77: the first match (the backtrack points it sets are no-ops under STSSched)."""
+
+
+class FirstAndLastBacktrack(AmbiguityResolutionStrategy):
+    """:80-107: the first match."""
+
+
+class LastOnlyStrategy(AmbiguityResolutionStrategy):
+    """:109-117: the last match."""
+    policy = T.WILDCARD_LAST
+
+    def resolve(self, msgSelector, pending, backtrackSetter=None):
+        matching = [i for i, m in enumerate(pending) if msgSelector(m)]
+        return matching[-1] if matching else None
+
+
+# ------------------------------------------------------------------ the trace as the clusterizers see it
+class _Deliveries:
+    """The UniqueMsgEvents of a trace: record index, Uniq id, message type, payload fields, external or not."""
+
+    def __init__(self, trace: EventTrace, model: Model):
+        ev = trace.events
+        self.n_rec = len(ev)
+        self.idx = [int(i) for i in np.nonzero(ev["kind"] == T.REC_MSG_EVENT)[0]]
+        self.ids = [int(ev["id"][i]) for i in self.idx]
+        assert len(set(self.ids)) == len(self.ids), "Must be UniqueMsgEvent: ids of the deliveries are not unique"
+        self.types = [int(ev["msg_type"][i]) for i in self.idx]
+        self.external = [model.msg_class[t] == T.MSG_EXTERNAL for t in self.types]      # EventTypes.isExternal
+        self.rec_of_id = dict(zip(self.ids, self.idx))
+        self.clock_inc = [t in model.clock_increment_types for t in self.types]       # causesClockIncrement
+        self.clock: List[Optional[int]] = []                                           # getLogicalClock
+        for i, t in zip(self.idx, self.types):
+            k = model.clock_field.get(t)
+            area = int(ev["p0"][i]) | int(ev["p1"][i]) << 16 | int(ev["p_hi"][i]) << 32
+            self.clock.append(None if k is None else int(T.payload_fields(area, model.payloads)[k]))
+
+    def present(self, include: Set[int]) -> np.ndarray:
+        """bool[n_rec]: the trace that holds the external deliveries and the deliveries whose id is in `include`."""
+        p = np.zeros(self.n_rec, dtype=bool)
+        for i, d, x in zip(self.idx, self.ids, self.external):
+            p[i] = x or d in include
+        return p
+
+
+class Clusterizer:
+    """Clusterizer.scala.  getNextTrace returns the presence mask (bool[n_rec]) of the next trace, or None."""
+    approximateIterations = 0
+
+    def getNextTrace(self, violationReproducedLastRun: bool, ignoredAbsentIds: Set[int]) -> Optional[np.ndarray]:
+        raise NotImplementedError
+
+    def selectors(self) -> Tuple[np.ndarray, np.ndarray]:
+        """(type_sets uint32[n_rec], policies uint8[n_rec]) of the trace's records: what a kept delivery is wildcarded to."""
+        raise NotImplementedError
+
+    def clone(self) -> "Clusterizer":
+        import copy
+        c = copy.copy(self)
+        for k, v in self.__dict__.items():
+            if isinstance(v, (_OneAtATimeIterator, _ClockClusterIterator)):
+                setattr(c, k, v.clone())
+        return c
+
+
+class SingletonClusterizer(Clusterizer):
+    """OneAtATimeClusterizer.scala: pick an event to remove, wildcard all the others."""
+
+    def __init__(self, originalTrace: EventTrace, model: Model, resolutionStrategy: AmbiguityResolutionStrategy):
+        self.d = _Deliveries(originalTrace, model)
+        self.resolutionStrategy = resolutionStrategy
+        self.sortedIds = sorted(i for i, x in zip(self.d.ids, self.d.external) if not x)        # getIdsToRemove
+        self.allIds = frozenset(self.d.ids)                                                    # | getUnignorableIds
+        self.successfullyRemoved: FrozenSet[int] = frozenset()
+        self.ignoredLastRun = -1
+        self.firstRun = True
+
+    @property
+    def approximateIterations(self):
+        return len(self.allIds)
+
+    def getNextTrace(self, violationReproducedLastRun, ignoredAbsentIds):
+        if not self.sortedIds:
+            return None
+        if violationReproducedLastRun:
+            self.successfullyRemoved = (self.successfullyRemoved | frozenset(ignoredAbsentIds)) | {self.ignoredLastRun}
+        if not self.firstRun:
+            self.ignoredLastRun = self.sortedIds[0]
+            self.sortedIds = self.sortedIds[1:]
+        else:
+            self.firstRun = False
+        currentCluster = self.allIds - (self.successfullyRemoved - {self.ignoredLastRun})
+        return self.d.present(currentCluster)
+
+    def selectors(self):
+        ts = np.zeros(self.d.n_rec, dtype=np.uint32)
+        po = np.zeros(self.d.n_rec, dtype=np.uint8)
+        for i, t, x in zip(self.d.idx, self.d.types, self.d.external):
+            if not x:
+                ts[i] = 1 << t                              # the class tag
+                po[i] = self.resolutionStrategy.policy
+        return ts, po
+
+
+class Aggressiveness:
+    """ClockClusterizer.scala:12-21."""
+    NONE, ALL_TIMERS_FIRST_ITR, STOP_IMMEDIATELY = 0, 1, 2
+
+
+class _ClockClusterIterator:
+    """ClockClusterIterator (ClockClusterizer.scala:138-228): the first iteration includes all events."""
+
+    def __init__(self, d: _Deliveries):
+        self.d = d
+        self.allIds = frozenset(i for i, inc, c in zip(d.ids, d.clock_inc, d.clock) if not inc and c is not None)
+        self.firstClusterRemoval = True
+        self.nextClockToRemove = -1
+        self.blacklist: FrozenSet[int] = frozenset()
+        self.clocks: List[int] = []
+        self.clocks = self.computeRemainingClocks()
+
+    def clone(self):
+        import copy
+        c = copy.copy(self)
+        c.clocks = list(self.clocks)
+        return c
+
+    def computeRemainingClocks(self) -> List[int]:
+        lowest = self.clocks[0] if self.clocks else 0
+        vals = {c for i, c in zip(self.d.ids, self.d.clock) if i not in self.blacklist and c is not None}
+        return [c for c in sorted(vals) if c >= lowest]
+
+    def _current(self) -> FrozenSet[int]:
+        currentClockToRemove = -1 if self.firstClusterRemoval else self.nextClockToRemove
+        out = set()
+        for i, inc, c in zip(self.d.ids, self.d.clock_inc, self.d.clock):
+            if inc:
+                continue                                    # handled by OneAtATimeIterator
+            if c is None or not (c == currentClockToRemove or i in self.blacklist):
+                out.add(i)
+        return frozenset(out)
+
+    def next(self) -> FrozenSet[int]:
+        if self.firstClusterRemoval:
+            ret = self._current()
+            self.firstClusterRemoval = False
+            return ret
+        self.nextClockToRemove = self.clocks[0]
+        ret = self._current()
+        self.clocks = self.clocks[1:]
+        return ret
+
+    def hasNext(self) -> bool:
+        return self.firstClusterRemoval or bool(self.clocks)
+
+    def producedViolation(self, previouslyIncluded, ignoredAbsents):
+        self.blacklist = self.blacklist | self.inverse(previouslyIncluded)
+        if ignoredAbsents:
+            self.blacklist = self.blacklist | (self.allIds & frozenset(ignoredAbsents))
+            self.clocks = self.computeRemainingClocks()
+
+    def inverse(self, toInclude):
+        return self.allIds - frozenset(toInclude)
+
+
+class _OneAtATimeIterator:
+    """OneAtATimeIterator (ClockClusterizer.scala:230-290): all timers, then all but the first, all but the second, ..."""
+
+    def __init__(self, all_ids):
+        self.all = frozenset(all_ids)
+        self.toRemove = sorted(self.all)
+        self.first = True
+        self.blacklist: FrozenSet[int] = frozenset()
+
+    def clone(self):
+        import copy
+        c = copy.copy(self)
+        c.toRemove = list(self.toRemove)
+        return c
+
+    def _current(self):
+        if self.first:
+            return self.all - self.blacklist
+        return (self.all - {self.toRemove[0]}) - self.blacklist
+
+    def next(self):
+        if self.first:
+            ret = self._current()
+            self.first = False
+            return ret
+        ret = self._current()
+        self.toRemove = self.toRemove[1:]
+        return ret
+
+    def hasNext(self):
+        return self.first or bool(self.toRemove)
+
+    def producedViolation(self, previouslyIncluded, ignoredAbsents):
+        self.blacklist = self.blacklist | self.inverse(previouslyIncluded) | (self.all & frozenset(ignoredAbsents))
+
+    def reset(self):
+        self.toRemove = sorted(self.all - self.blacklist)
+        self.first = True
+
+    def inverse(self, toInclude):
+        return self.all - frozenset(toInclude)
+
+
+class ClockClusterizer(Clusterizer):
+    """ClockClusterizer.scala:23-135: cluster the deliveries by their logical clock, and for every cluster try the timers
+    (the messages that cause a clock increment) one at a time."""
+
+    def __init__(self, originalTrace: EventTrace, model: Model, resolutionStrategy: AmbiguityResolutionStrategy,
+                 aggressiveness: int = Aggressiveness.ALL_TIMERS_FIRST_ITR, skipClockClusters: bool = False):
+        self.d = _Deliveries(originalTrace, model)
+        self.model = model
+        self.resolutionStrategy = resolutionStrategy
+        self.aggressiveness = aggressiveness
+        self.skipClockClusters = skipClockClusters
+        self.clusterIterator = _ClockClusterIterator(self.d)
+        assert self.clusterIterator.hasNext()
+        self.currentCluster = self.clusterIterator.next()         # start by not removing any clusters
+        self.tryingFirstCluster = True
+        self.timerIterator = _OneAtATimeIterator(i for i, inc in zip(self.d.ids, self.d.clock_inc) if inc)
+        self.currentTimers: FrozenSet[int] = frozenset()
+
+    @property
+    def approximateIterations(self):
+        if self.skipClockClusters:
+            return len(self.timerIterator.toRemove)
+        return len(self.clusterIterator.clocks) * len(self.timerIterator.toRemove)
+
+    def getNextTrace(self, violationReproducedLastRun, ignoredAbsentIds):
+        if violationReproducedLastRun:
+            self.timerIterator.producedViolation(self.currentTimers, ignoredAbsentIds)
+            self.clusterIterator.producedViolation(self.currentCluster, ignoredAbsentIds)
+        if (not self.timerIterator.hasNext() or
+                (self.aggressiveness == Aggressiveness.ALL_TIMERS_FIRST_ITR and violationReproducedLastRun
+                 and not self.tryingFirstCluster) or
+                (self.aggressiveness == Aggressiveness.STOP_IMMEDIATELY and violationReproducedLastRun)):
+            self.tryingFirstCluster = False
+            if not self.clusterIterator.hasNext() or self.skipClockClusters:
+                return None
+            self.timerIterator.reset()
+            self.currentCluster = self.clusterIterator.next()
+        assert self.timerIterator.hasNext()
+        self.currentTimers = self.timerIterator.next()
+        return self.d.present(self.currentTimers | self.currentCluster)
+
+    def selectors(self):
+        ts = np.zeros(self.d.n_rec, dtype=np.uint32)
+        po = np.zeros(self.d.n_rec, dtype=np.uint8)
+        inc_set = sum(1 << t for t in self.model.clock_increment_types)
+        for i, t, x, inc in zip(self.d.idx, self.d.types, self.d.external, self.d.clock_inc):
+            if x:
+                continue
+            if inc:                 # timers bypass the resolutionStrategy: lst.indexWhere(causesClockIncrement)
+                ts[i], po[i] = inc_set, T.WILDCARD_FIRST
+            else:
+                ts[i], po[i] = 1 << t, self.resolutionStrategy.policy
+        return ts, po
+
+
+# ------------------------------------------------------------------ the replay oracle on the GPU
+class StsWildcardOracle:
+    """RunnerUtils.testWithStsSched (RunnerUtils.scala:913-943) for the traces a Clusterizer proposes: K2 with wildcard
+    deliveries (demi_replay_wildcard_*).  `trace.original_externals` is the MCS: every external is kept."""
+
+    def __init__(self, schedulerConfig: SchedulerConfig, device: int = 0, p_max: int = 64):
+        if schedulerConfig.model is None or schedulerConfig.model.inv_kind == T.INV_NONE:
+            raise ValueError("Must invoke setInvariant before test()")
+        if int(schedulerConfig.filterKnownAbsents):
+            raise ValueError("the wildcard replay is built for filterKnownAbsents = false only")
+        self.schedulerConfig = schedulerConfig
+        self.p_max = p_max
+        self._ctx = _native.Context(device)
+        self._ctx.model_load(schedulerConfig.model.to_struct())
+        if getattr(schedulerConfig.model, "compiled_only", False):
+            self._ctx.model_specialize()
+        self._trace = None
+        self.launches = 0
+        self.batches: List[int] = []
+
+    def _limits(self, fp: ViolationFingerprint, p_max=None) -> T.Limits:
+        return T.Limits(0, 0, p_max or self.p_max, 1, fp.code, 1 if self.schedulerConfig.populate_all_actors else 0, 0, 0)
+
+    def load(self, trace: EventTrace, type_sets, policies):
+        self._ctx.replay_load(trace.original_externals, trace.events)
+        self._ctx.replay_wildcard_load(type_sets, policies)
+        self._trace = trace
+
+    def test_batch(self, presents: Sequence[np.ndarray], violation: ViolationFingerprint) -> List[bool]:
+        from .schedulers import CapacityExceeded, OVF_FLAGS
+        presents = np.asarray(presents, dtype=bool).reshape(len(presents), -1)
+        self.launches += 1
+        self.batches.append(len(presents))
+        v = self._ctx.replay_wildcard_batch(presents, self._limits(violation))
+        bad = np.nonzero(v["flags"] & OVF_FLAGS)[0]
+        if len(bad):      # a replay aborted on a capacity is no answer: repeat it with the largest pending set, else give up loudly
+            self.launches += 1
+            v[bad] = self._ctx.replay_wildcard_batch(presents[bad], self._limits(violation, T.MAX_PENDING))
+            if (v["flags"] & OVF_FLAGS).any():
+                raise CapacityExceeded("a wildcard candidate's replay exceeds the engine's capacities")
+        return [bool(f & T.V_VIOLATION) for f in v["flags"]]
+
+    def executed(self, present: np.ndarray, violation: ViolationFingerprint):
+        """test() of one candidate: (executed trace, record indices of the present deliveries that were ignored as absent)
+        iff it triggers the violation, else None."""
+        from .schedulers import CapacityExceeded, OVF_FLAGS
+        self.launches += 1
+        v, kept, rec = self._ctx.replay_wildcard_get_trace(present, self._limits(violation))
+        if (int(v.flags) & OVF_FLAGS) and self.p_max < T.MAX_PENDING:
+            self.launches += 1
+            v, kept, rec = self._ctx.replay_wildcard_get_trace(present, self._limits(violation, T.MAX_PENDING))
+        if int(v.flags) & OVF_FLAGS:
+            raise CapacityExceeded("the replay exceeds the engine's capacities")
+        if not (int(v.flags) & T.V_VIOLATION):
+            return None
+        ev = self._trace.events
+        ignored = {int(i) for i in np.nonzero((ev["kind"] == T.REC_MSG_EVENT) & np.asarray(present, dtype=bool) & (kept == 0))[0]}
+        return EventTrace(rec, self._trace.original_externals), ignored
+
+    def shutdown(self):
+        self._ctx.close()
+
+
+# ------------------------------------------------------------------ WildcardMinimizer.scala
+class ClusteringStrategy:
+    ClockClusterizer, SingletonClusterizer, ClockThenSingleton = "ClockClusterizer", "SingletonClusterizer", "ClockThenSingleton"
+
+
+class WildcardMinimizer:
+    """WildcardMinimizer.scala:44-242 with TestScheduler.STSSched.  `oracle`: a StsWildcardOracle (created, and shut down, here
+    when None).  `max_batch` bounds how many of the clusterizer's upcoming proposals are replayed per launch."""
+
+    def __init__(self, schedulerConfig: SchedulerConfig, mcs: np.ndarray, trace: EventTrace, violation: ViolationFingerprint,
+                 skipClockClusters: bool = False, resolutionStrategy: Optional[AmbiguityResolutionStrategy] = None,
+                 clusteringStrategy: str = ClusteringStrategy.ClockClusterizer, stats: Optional[MinimizationStats] = None,
+                 max_batch: int = 1 << 14, oracle=None, device: int = 0, p_max: int = 64):
+        self.schedulerConfig = schedulerConfig
+        self.mcs = mcs
+        self.trace = EventTrace(trace.events, mcs)
+        self.violation = violation
+        self.skipClockClusters = skipClockClusters
+        self.resolutionStrategy = resolutionStrategy if resolutionStrategy is not None else BackTrackStrategy()
+        self.clusteringStrategy = clusteringStrategy
+        self._stats = stats or MinimizationStats()
+        self.max_batch = max(1, int(max_batch))
+        self.oracle = oracle
+        self._device, self._p_max = device, p_max
+        self.proposals: List[np.ndarray] = []          # every trace the sequential loop tested, in order (presence masks)
+        self.internal_sizes: List[int] = []            # record_internal_size after every (sequential) replay
+        self.speculative_replays = 0
+        self.batches: List[int] = []
+
+    def minimize(self) -> Tuple[MinimizationStats, EventTrace]:
+        model = self.schedulerConfig.model
+        aggressiveness = Aggressiveness.STOP_IMMEDIATELY if self.skipClockClusters else Aggressiveness.ALL_TIMERS_FIRST_ITR
+        own = self.oracle is None
+        if own:
+            self.oracle = StsWildcardOracle(self.schedulerConfig, device=self._device, p_max=self._p_max)
+        try:
+            if self.clusteringStrategy in (ClusteringStrategy.ClockClusterizer, ClusteringStrategy.ClockThenSingleton):
+                clusterizer = ClockClusterizer(self.trace, model, self.resolutionStrategy, aggressiveness=aggressiveness,
+                                               skipClockClusters=self.skipClockClusters)
+            else:
+                clusterizer = SingletonClusterizer(self.trace, model, self.resolutionStrategy)
+            minTrace = self.doMinimize(clusterizer, self.trace)
+            if self.clusteringStrategy == ClusteringStrategy.ClockThenSingleton:
+                minTrace = self.doMinimize(SingletonClusterizer(minTrace, model, self.resolutionStrategy), minTrace)
+            if not self.skipClockClusters:
+                self.internal_sizes.append(countMsgEvents(minTrace))          # fencepost
+            return self._stats, minTrace
+        finally:
+            if own:
+                self.oracle.shutdown()
+                self.oracle = None
+
+    def doMinimize(self, clusterizer: Clusterizer, startTrace: EventTrace) -> EventTrace:
+        minTrace = startTrace
+        d = clusterizer.d
+        id_of_rec = {i: k for k, i in d.rec_of_id.items()}
+        self.oracle.load(startTrace, *clusterizer.selectors())
+        last = (False, frozenset())                     # what the next getNextTrace is told about the last run
+        while True:
+            # the clusterizer's upcoming proposals, each assuming the one before it failed
+            spec = clusterizer.clone()
+            cands: List[np.ndarray] = []
+            args = last
+            while len(cands) < self.max_batch:
+                p = spec.getNextTrace(*args)
+                if p is None:
+                    break
+                cands.append(p)
+                args = (False, frozenset())
+            if not cands:
+                assert clusterizer.getNextTrace(*last) is None
+                break
+            results = self.oracle.test_batch(cands, self.violation)
+            self.speculative_replays += len(cands)
+            self.batches.append(len(cands))
+            j = next((k for k, r in enumerate(results) if r), None)
+            consumed = len(cands) if j is None else j + 1
+            args = last
+            for k in range(consumed):                   # bring the real clusterizer to where the sequential loop would be
+                p = clusterizer.getNextTrace(*args)
+                assert p is not None and (p == cands[k]).all()
+                self.proposals.append(p)
+                if not self.skipClockClusters:
+                    self.internal_sizes.append(countMsgEvents(minTrace))
+                args = (False, frozenset())
+            self._stats.increment_replays(consumed)
+            if j is None:
+                last = (False, frozenset())
+                continue
+            got = self.oracle.executed(cands[j], self.violation)
+            assert got is not None, "batched and single replay of the same candidate disagree"
+            ret, ignoredAbsentIndices = got
+            ret = EventTrace(ret.events, self.mcs)
+            if len(ret.events) <= len(minTrace.events):
+                minTrace = ret
+            last = (True, frozenset(id_of_rec[i] for i in ignoredAbsentIndices))
+        return minTrace
+
+
+def wildcardMinimize(schedulerConfig: SchedulerConfig, mcs: np.ndarray, trace: EventTrace, violation: ViolationFingerprint,
+                     **kw) -> Tuple[MinimizationStats, EventTrace]:
+    return WildcardMinimizer(schedulerConfig, mcs, trace, violation, **kw).minimize()

@@ -459,6 +459,42 @@ int demi_replay_get_kept(demi_ctx* ctx, const uint64_t* mask /* [4] or NULL */, 
 uint32_t demi_replay_recorded_len(const demi_ctx* ctx);
 /* Number of external events of that execution (0 without one): the length demi_ddmin's `conjoined` must have. */
 uint32_t demi_replay_externals_len(const demi_ctx* ctx);
+
+/* ---------------------------------------------------------- K2W: the replay oracle of the wildcard minimizers
+ * WildcardMinimizer (minification/wildcard_minimization/WildcardMinimizer.scala) with TestScheduler.STSSched: a Clusterizer
+ * proposes traces over the SAME original trace in which every kept internal or timer delivery is a
+ * MsgEvent(snd, rcv, WildCardMatch(selector)) and the deliveries outside the current cluster are dropped (their MsgSends
+ * stay); RunnerUtils.testWithStsSched (RunnerUtils.scala:913-943) replays each with STSScheduler.test.  A wildcard is
+ * pending iff its selector picks one of the pending messages of (snd, rcv), taken in send order (STSScheduler.scala:380-402),
+ * and delivers the head of the fingerprint group its selector picks (:696-711); what it delivers may differ from the
+ * recorded message, so the replay leaves the recorded execution.  With STSSched's no-op backtrack setter every selector of
+ * the reference is a set of message types (the class tag; causesClockIncrement for ClockClusterizer's timers) and one of: */
+typedef enum {
+  DEMI_WILDCARD_HEAD = 0,   /* SrcDstFIFOOnly: the least recently sent pending message of (snd, rcv) must match */
+  DEMI_WILDCARD_FIRST = 1,  /* BackTrackStrategy, FirstAndLastBacktrack, the timer wildcard: the first match */
+  DEMI_WILDCARD_LAST = 2    /* LastOnlyStrategy: the last match (when delivering: the head of the last matching group) */
+} demi_wildcard_policy;
+/* The selectors of the execution loaded by demi_replay_load, one per recorded event (entries of events that are not
+ * MsgEvents are ignored): type_sets[i] bit t = message type t matches, 0 = the exact delivery of demi_replay_batch;
+ * policies[i] a demi_wildcard_policy.  One load serves every candidate of a Clusterizer.  DEMI_ERR_INVALID_ARG: a table of
+ * more than 8 actors, a DEMI_MODEL_PAYLOADS or DEMI_MODEL_ARRAY table (not built; never replayed with other semantics). */
+int demi_replay_wildcard_load(demi_ctx* ctx, const uint32_t* type_sets /* [n_rec] */, const uint8_t* policies /* [n_rec] */);
+/* n candidates: masks as in demi_replay_batch (NULL: every external kept); present[c] is a bitmask over the recorded events
+ * (ceil(n_rec / 64) words, bit i of word i / 64): a MsgEvent whose bit is 0 is not part of candidate c's trace (with all
+ * ones but one this is demi_replay_removal_batch's `skip`; bits of other kinds are ignored).  Verdicts as in
+ * demi_replay_batch; a replay that exceeds limits->p_max has DEMI_V_PENDING_OVF set and is no verdict.
+ * limits->filter_known_absents must be 0 (DEMI_ERR_INVALID_ARG otherwise). */
+int demi_replay_wildcard_batch(demi_ctx* ctx, const uint64_t* masks /* [n][4] or NULL */, const uint64_t* present /* [n][words] */,
+                               uint64_t n, const demi_limits* limits, demi_verdict* out);
+/* One candidate once more, recorded.  kept[i] (demi_replay_recorded_len entries) = 1 iff recorded event i is lowered and took
+ * effect: a present MsgEvent with kept 0 was ignored as absent (the index the IgnoreAbsentCallback receives).  rec_out: the
+ * executed EventTrace (what STSScheduler.test returns, STSScheduler.scala:286-292) in the convention of demi_replay_get_kept -
+ * the applied external events, the external MsgSends, every MsgEvent with the message it actually delivered, and the MsgSend
+ * of every delivered internal or timer message where it was sent; Uniq ids numbered 1, 2, ... in order of appearance.
+ * demi_replay_load accepts it in turn.  *n_out = its length; DEMI_ERR_CAPACITY if cap is smaller (0 with an aborted replay). */
+int demi_replay_wildcard_get_trace(demi_ctx* ctx, const uint64_t* mask /* [4] or NULL */, const uint64_t* present /* [words] */,
+                                   const demi_limits* limits, demi_verdict* verdict, uint8_t* kept, demi_rec_event* rec_out,
+                                   uint32_t cap, uint32_t* n_out);
 /* external events of the trace demi_trace_load holds (0: none) - what demi_random_ddmin's `conjoined` array must cover */
 uint32_t demi_trace_len(const demi_ctx* ctx);
 
