@@ -311,8 +311,7 @@ inline std::string generate_vm(const demi::DevModel& h, bool sched = false) {
   // Optional if-conversion (DEMI_JIT_IFCONVERT = longest guarded run, 0 / unset = off): a fused guard over a short
   // run of pure ALU rows, none of which is a jump target or a handler entry, becomes selects instead of a branch
   // (fewer exec-mask manipulations on the scalar unit).  Same semantics: a skipped ALU row leaves its register alone.
-  uint32_t ifconv = 0;
-  if (const char* e = demi_host::knob("DEMI_JIT_IFCONVERT")) { const long x = strtol(e, nullptr, 10); ifconv = x > 0 && x < 16 ? (uint32_t)x : 0; }
+  const uint32_t ifconv = (uint32_t)demi_host::knob_int("DEMI_JIT_IFCONVERT", 1, 15, 0);
   std::vector<uint8_t> is_target(h.code_len + 1, 0);
   for (uint32_t st : starts) is_target[st] = 1;
   for (uint32_t pc = 0; pc < h.code_len; pc++) {

@@ -15,4 +15,11 @@ inline const char* knob(const char* name) {
   const char* e = getenv("DEMI_EXPERIMENT");       // (read every time: a test process switches it on before it sets a knob)
   return (e && e[0] == '1' && e[1] == 0) ? getenv(name) : nullptr;
 }
+// an integer knob: its value when it is set and lies in [lo, hi], else `fallback` (a value outside the range is ignored)
+inline long knob_int(const char* name, long lo, long hi, long fallback) {
+  const char* e = knob(name);
+  if (!e) return fallback;
+  const long x = strtol(e, nullptr, 10);
+  return (x >= lo && x <= hi) ? x : fallback;
+}
 }  // namespace demi_host

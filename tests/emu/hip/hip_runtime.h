@@ -52,6 +52,8 @@ extern "C" {
 void w64_launch(dim3 grid, dim3 block, size_t lds_bytes, void (*body)(void*), void* arg);
 int w64_num_cu();
 int w64_occupancy();
+void w64_count_allocation(int delta);     // live hipMalloc / hipHostMalloc allocations (w64_live_allocations, read by the tests)
+int w64_refuse_compiled();                // W64_REFUSE_COMPILED=1: the occupancy query of a compiled (module) kernel fails
 }
 
 static inline const char* hipGetErrorString(hipError_t e) { return e == hipSuccess ? "hipSuccess" : "emulated HIP error"; }
@@ -72,11 +74,12 @@ template <class T> static inline hipError_t hipMalloc(T** p, size_t n) {
   if (posix_memalign(&q, 256, n ? n : 1) != 0) return hipErrorOutOfMemory;
   memset(q, 0xA5, n);          // (fresh device memory holds no promises either)
   *p = static_cast<T*>(q);
+  w64_count_allocation(+1);
   return hipSuccess;
 }
 template <class T> static inline hipError_t hipHostMalloc(T** p, size_t n, unsigned = 0) { return hipMalloc(p, n); }
-static inline hipError_t hipFree(void* p) { free(p); return hipSuccess; }
-static inline hipError_t hipHostFree(void* p) { free(p); return hipSuccess; }
+static inline hipError_t hipFree(void* p) { if (p) w64_count_allocation(-1); free(p); return hipSuccess; }
+static inline hipError_t hipHostFree(void* p) { return hipFree(p); }
 static inline hipError_t hipMemcpy(void* d, const void* s, size_t n, hipMemcpyKind) { if (n) memmove(d, s, n); return hipSuccess; }
 static inline hipError_t hipMemcpyAsync(void* d, const void* s, size_t n, hipMemcpyKind, hipStream_t = nullptr) { if (n) memmove(d, s, n); return hipSuccess; }
 static inline hipError_t hipMemset(void* d, int v, size_t n) { if (n) memset(d, v, n); return hipSuccess; }
@@ -104,7 +107,7 @@ template <class F> static inline hipError_t hipOccupancyMaxActiveBlocksPerMultip
   return hipSuccess;
 }
 static inline hipError_t hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(int* n, hipFunction_t, int, size_t lds) {
-  if (lds > 160 * 1024) return hipErrorInvalidValue;
+  if (lds > 160 * 1024 || w64_refuse_compiled()) return hipErrorInvalidValue;
   *n = w64_occupancy();
   return hipSuccess;
 }

@@ -261,6 +261,12 @@ extern "C" void w64_block_barrier(int line) {
 
 extern "C" int w64_num_cu() { return env_int("W64_NUM_CU", 2, 1, 64); }
 extern "C" int w64_occupancy() { return env_int("W64_OCCUPANCY", 2, 1, 8); }
+extern "C" int w64_refuse_compiled() { return env_int("W64_REFUSE_COMPILED", 0, 0, 1); }
+
+// allocations made and not yet freed: a context that is destroyed must leave none behind (tests/test_emu_suite_cpu.py)
+static std::atomic<long> g_live_allocations{0};
+extern "C" void w64_count_allocation(int delta) { g_live_allocations += delta; }
+extern "C" long w64_live_allocations() { return g_live_allocations.load(); }
 
 extern "C" void w64_launch(dim3 grid, dim3 block, size_t lds_bytes, void (*body)(void*), void* arg) {
   if (lds_bytes > sizeof demi::smem) die("dynamic LDS beyond 160 KB", (int)lds_bytes);
@@ -277,7 +283,13 @@ extern "C" void w64_launch(dim3 grid, dim3 block, size_t lds_bytes, void (*body)
       const uint64_t i = next.fetch_add(1);
       if (i >= n_groups) break;
       memset(demi::smem, 0xCD, lds_bytes);     // LDS starts undefined
+      // a guard behind the workgroup's dynamic LDS: a kernel that carves more than the host sized writes into its neighbour's on the device
+      unsigned char* const guard = reinterpret_cast<unsigned char*>(demi::smem) + lds_bytes;
+      const size_t n_guard = std::min<size_t>(256, sizeof demi::smem - lds_bytes);
+      memset(guard, 0x5C, n_guard);
       run_group(grid, block, (unsigned)(i % grid.x), (unsigned)((i / grid.x) % grid.y), (unsigned)(i / ((uint64_t)grid.x * grid.y)), body, arg);
+      for (size_t k = 0; k < n_guard; k++)
+        if (guard[k] != 0x5C) die("a workgroup wrote behind its dynamic LDS; launched with bytes =", (int)lds_bytes);
     }
   };
   if (n_thr <= 1) { work(); return; }

@@ -167,3 +167,80 @@ def test_results_do_not_depend_on_the_order_of_the_lanes_within_an_interval():
                   "test_k2_gpu.py::test_filter_known_absents_parity[hbm]"], lane_order="reverse")
     run_emulated(["test_k3_gpu.py::test_per_interleaving_outputs_match_the_oracle",
                   "test_provenance_gpu.py", "test_zz_array_gpu.py::test_raft_with_a_real_log_through_the_kernels"], threads=1, lane_order="shuffle:7")
+
+
+_LIFETIME_DRIVER = r"""
+import ctypes, os, sys
+import numpy as np
+sys.path.insert(0, os.getcwd())
+from tests.emu import build
+b = build.build()
+os.environ["DEMI_NO_TORCH"] = "1"
+os.environ["DEMI_HIPRTC_LIB"] = b["hiprtc"]
+from demi_amd import _native, types as T
+from demi_amd.apps import raft5_config2, raft5_dpor_config3
+_native.LIB_PATH = b["lib"]
+live = ctypes.CDLL(b["runtime"]).w64_live_allocations
+live.restype = ctypes.c_long
+
+def cycle(specialise):
+    model, events, lim = raft5_config2()
+    ctx = _native.Context(0)
+    ctx.model_load(model.to_struct())
+    if specialise:
+        ctx.model_specialize()
+    ctx.trace_load(events)
+    got = ctx.random_explore(256, lim, seed_base=0x5EED0000)                       # a K1 launch
+    bad = np.nonzero(got["flags"] & T.V_VIOLATION)[0]
+    assert len(bad)
+    tickets = [ctx.random_explore_submit(128, lim, seed_base=0x5EED0000 + 128 * k, want_verdicts=(k == 1)) for k in range(3)]
+    for k, t in enumerate(tickets):                                                # submit / wait
+        ctx.random_explore_wait(t, out=np.zeros(128, dtype=T.VERDICT_DTYPE) if k == 1 else None)
+    v, rec = ctx.random_get_trace(0x5EED0000 + int(bad[0]), lim)
+    rlim = T.Limits(0, 0, 128, 1, v.fingerprint, 0)
+    ctx.replay_load(events, rec)
+    masks = np.zeros((8, 4), dtype=np.uint64)
+    masks[:, 0] = (1 << 50) - 1
+    ctx.replay_batch(masks, rlim)                                                  # a replay batch
+    is_ev = rec["kind"] == T.REC_MSG_EVENT
+    ctx.replay_wildcard_load(np.where(is_ev, np.uint32(1) << rec["msg_type"].astype(np.uint32), 0).astype(np.uint32),
+                             np.full(len(rec), T.WILDCARD_FIRST, dtype=np.uint8))
+    ctx.replay_wildcard_batch(np.ones((4, len(rec)), dtype=bool), rlim)            # a wildcard batch
+    ctx.ddmin(rlim)                                                                # demi_ddmin
+    ctx.random_ddmin(T.Limits(len(rec), 0, 128, 1, v.fingerprint, 0), T.RandomDdminParams(8, 0, 16), seed_base=0x5EED0000)
+    model3, ev3, par = raft5_dpor_config3()
+    ctx.model_load(model3.to_struct())
+    if specialise:
+        ctx.model_specialize()
+    ctx.dpor_load(ev3)
+    for order in (T.DPOR_ORDER_ROUNDS, T.DPOR_ORDER_REFERENCE):                    # a DPOR exploration in both orders
+        ctx.dpor_explore(par, T.DporSearch(64, 300, 0, 1, order))
+    ctx.close()
+
+_native.lib()
+base = live()
+seen = []
+for specialise in (False, True, False):
+    cycle(specialise)
+    seen.append(live() - base)
+print("live allocations after each create / run / destroy cycle:", seen)
+assert seen == [0, 0, 0], seen
+"""
+
+
+def test_no_buffer_outlives_its_context():
+    """Every device and pinned allocation a context makes is gone when it is destroyed: the emulator counts hipMalloc /
+    hipHostMalloc against hipFree / hipHostFree (w64_live_allocations), and three create / run / destroy cycles - a K1 launch,
+    submit / wait, a replay batch, a wildcard batch, demi_ddmin, demi_random_ddmin, a DPOR exploration in both orders, interpreted
+    and compiled, no knob set - end where they began."""
+    env = {k: v for k, v in os.environ.items() if not k.startswith("DEMI_")}
+    out = subprocess.run([sys.executable, "-c", _LIFETIME_DRIVER], cwd=ROOT, env=dict(env, W64_THREADS="1"), capture_output=True, text=True, timeout=1500)
+    assert out.returncode == 0, (out.stdout + out.stderr)[-4000:]
+
+
+def test_a_refused_compiled_kernel_is_launched_as_the_generic_one_with_its_own_sizes():
+    """W64_REFUSE_COMPILED=1 makes the occupancy query of every compiled kernel fail: each launch falls back to the generic kernel
+    (the tables here are not compiled-only) and must size its LDS for THAT kernel - the emulator aborts a launch whose
+    workgroups write behind their dynamic LDS."""
+    run_emulated(["test_k1_gpu.py::test_small_launches_on_few_lanes_of_many_waves", "test_random_ddmin_gpu.py"],
+                 extra_env={"W64_REFUSE_COMPILED": "1"})
