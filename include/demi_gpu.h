@@ -230,7 +230,12 @@ typedef struct {
  * in both orders with the device-resident queue and the checkpoints, demi_provenance_prune (which reads its traces in the layout
  * of the table the context holds).  Tables of up to 8 actors are untouched: same layout, same
  * verdict hashes, the same instructions in their kernels (the message word of the small layout has no room for a second
- * layout's fields, so the big one is a layout of its own rather than a widening of the old).  tests/test_big_gpu.py. */
+ * layout's fields, so the big one is a layout of its own rather than a widening of the old).  tests/test_big_gpu.py.
+ * One combination does not fit the 160 KB of LDS: DEMI_STRATEGY_SRC_DST_FIFO (256 (src, dst) queues per schedule) on a BIG table
+ * near DEMI_MAX_CODE rows whose effect rows admit no compact effect schedule - demi_model_load accepts the table (the strategy
+ * is a parameter of the launch); demi_random_explore* / demi_random_get_trace then refuse that launch, DEMI_ERR_INVALID_ARG
+ * "LDS budget exceeded", from 15 actors on under a 64-event trace (14 with DEMI_MAX_EXT_EVENTS events; demi_random_get_trace
+ * under SrcDstFIFO from 12).  FullyRandom runs such a table at 16 actors.  tests/test_limits_gpu.py. */
 
 /* DEMI_MODEL_ARRAY(n): every actor owns, beside its eight state fields, an ARRAY of n elements (1..DEMI_MAX_ARRAY) of the
  * register window's width (u8, or u16 with DEMI_MODEL_WIDE) - the part of an actor's state that eight fields cannot hold: a

@@ -97,6 +97,29 @@ def test_tables_of_more_than_eight_actors_on_the_cpu():
                  threads=1, lane_order="reverse", timeout=2400)
 
 
+def test_limits_tables_crafted_seeds_and_capacity_edges_on_the_cpu():
+    """tests/test_limits_gpu.py, its cheapest cases: the narrow limits table (32 message types, 4 classes, 4 timer types up to id
+    31, ~970 rows) through K1 plain / SrcDstFIFO / SPREAD / carried / recording / candidate frontier / submit-wait, interpreted;
+    the seeds whose k-th draw takes nextInt's retry branch; every capacity from both sides on K1, K2 and K3; the re-binned kernel
+    and the compiled kernel with LDS-resident pending slots; one K2 and one K3 case on the limits table."""
+    run_emulated(["test_limits_gpu.py::test_model_load_refuses_one_step_beyond_each_limit",
+                  "test_limits_gpu.py::test_limits_tables_through_every_k1_variant[narrow-False]",
+                  "test_limits_gpu.py::test_crafted_seeds_through_every_k1_variant[raft5-True]",
+                  "test_limits_gpu.py::test_crafted_seeds_through_every_k1_variant[limits-False]",
+                  "test_limits_gpu.py::test_every_k1_capacity_from_both_sides[False]",
+                  "test_limits_gpu.py::test_every_k1_capacity_from_both_sides[True]",
+                  "test_limits_gpu.py::test_k2_capacities_at_the_edge[False]",
+                  "test_limits_gpu.py::test_k2_capacities_at_the_edge[True]",
+                  "test_limits_gpu.py::test_three_timer_types_at_ids_up_to_31[True]",
+                  "test_limits_gpu.py::test_k3_capacities_from_both_sides[False]",
+                  "test_limits_gpu.py::test_rebinned_kernel_against_the_plain_launch_and_the_oracle[raft5]",
+                  "test_limits_gpu.py::test_compiled_k1_with_lds_resident_pending_slots[raft5-3]",
+                  "test_limits_gpu.py::test_compiled_k1_with_lds_resident_pending_slots[limits-11]",
+                  "test_limits_gpu.py::test_limits_tables_replay_in_every_k2_mode[narrow-False-wave]",
+                  "test_limits_gpu.py::test_wildcards_whose_type_set_holds_bit_31[narrow-False]"])
+    run_emulated(["test_limits_gpu.py::test_limits_tables_dpor_in_both_orders[narrow-False]"], threads=1)
+
+
 def test_k2_sources_against_the_oracle_on_the_cpu():
     run_emulated(["test_k2_gpu.py::test_replay_parity_random_subsequences_raft5",
                   "test_k2_gpu.py::test_bench_candidates_against_the_sts_transliterations_record",

@@ -71,7 +71,9 @@ class ScalaRandomScheduler:
         """strategy: the FullyRandom of an earlier execution of the same scheduler instance (reset_all_state keeps the object
         and calls pendingEvents.clear(), RandomScheduler.scala:584: its Random is not reseeded)."""
         self.oracle, self.model, self.ms = oracle, model, model.to_struct()
-        self.trace = [tuple(int(x) for x in (e["kind"], e["a"], e["b"], e["msg_type"], e["p0"], e["p1"])) for e in trace]
+        # (an external Send's payload: the low bytes and, for a wide table, demi_ext_event.p0_hi / p1_hi)
+        self.trace = [tuple(int(x) for x in (e["kind"], e["a"], e["b"], e["msg_type"], int(e["p0"]) | int(e["p0_hi"]) << 8,
+                                             int(e["p1"]) | int(e["p1_hi"]) << 8)) for e in trace]
         self.maxMessages = maxMessages if maxMessages else (1 << 31) - 1
         self.invariant_check_interval = invariant_check_interval
         A = model.n_actors
