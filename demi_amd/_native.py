@@ -18,7 +18,8 @@ EXPORTS = ["demi_ctx_create", "demi_ctx_destroy", "demi_last_error", "demi_versi
            "demi_specialize_check", "demi_specialize_source", "demi_specialize_source_k1", "demi_provenance_prune", "demi_device_probe", "demi_device_probe_mix", "demi_calib_rw", "demi_random_explore_flagged", "demi_collect_flagged_dev", "demi_random_explore_submit", "demi_random_explore_wait", "demi_trace_len",
            "demi_comm_unique_id", "demi_comm_create", "demi_comm_create_host", "demi_comm_destroy", "demi_comm_rank",
            "demi_comm_allgather_dev", "demi_random_explore_sharded", "demi_replay_batch_sharded", "demi_abi_version", "demi_replay_externals_len", "demi_edit_distance_dpor_ddmin", "demi_dpor_explored", "demi_random_ddmin", "demi_random_explore_candidates", "demi_ext_payload_areas",
-           "demi_replay_wildcard_load", "demi_replay_wildcard_batch", "demi_replay_wildcard_get_trace"]
+           "demi_replay_wildcard_load", "demi_replay_wildcard_batch", "demi_replay_wildcard_get_trace",
+           "demi_replay_wildcard_candidates", "demi_wildcard_ddmin"]
 
 _lib = None
 ALLGATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t)     # demi_allgather_fn
@@ -101,6 +102,11 @@ def lib():
     L.demi_replay_wildcard_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(T.Limits), C.c_void_p]
     L.demi_replay_wildcard_get_trace.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(T.Limits), C.POINTER(T.Verdict),
                                                  C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]
+    L.demi_replay_wildcard_candidates.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(T.Limits),
+                                                  C.c_void_p, C.c_void_p]
+    L.demi_wildcard_ddmin.argtypes = [C.c_void_p, C.POINTER(T.Limits), C.POINTER(T.DdminParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
+                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32,
+                                      C.POINTER(T.DdminStats), C.POINTER(T.WildcardDdminResult)]
     L.demi_replay_get_kept.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(T.Limits), C.POINTER(T.Verdict),
                                        C.c_void_p]
     L.demi_dpor_load.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
@@ -434,6 +440,52 @@ class Context:
         self._check(lib().demi_replay_wildcard_get_trace(self._h, mp, (pw if pw.size else dummy).ctypes.data, C.byref(limits),
                                                          C.byref(v), kept.ctypes.data, rec.ctypes.data, cap, C.byref(n_out)))
         return v, kept[:n_rec], rec[:n_out.value].copy()
+
+    def _base_present(self, base_present):
+        import numpy as np
+        if base_present is None:
+            return None
+        n_rec = int(lib().demi_replay_recorded_len(self._h))
+        pw = self._present_words(np.asarray(base_present).reshape(1, -1), n_rec)
+        return pw if pw.size else np.zeros((1, 1), dtype=np.uint64)
+
+    def replay_wildcard_candidates(self, masks, drops, limits, base_present=None, want_all=False):
+        """One WildcardTestOracle.test per row of `masks` (demi_replay_wildcard_candidates): proposal 0 is `base_present`
+        (bool[n_rec]; None: every delivery), proposal j >= 1 that row without the MsgEvent recorded at drops[j - 1].  Returns the
+        reduced records (WILDCARD_CANDIDATE_DTYPE[n_cand]), with want_all also the verdict plane [n_cand, 1 + len(drops)]."""
+        import numpy as np
+        m = np.ascontiguousarray(masks, dtype=np.uint64).reshape(-1, 4)
+        d = np.ascontiguousarray(drops, dtype=np.uint32).reshape(-1)
+        out = np.zeros(len(m), dtype=T.WILDCARD_CANDIDATE_DTYPE)
+        plane = np.zeros((len(m), len(d) + 1), dtype=T.VERDICT_DTYPE) if want_all else None
+        bp = self._base_present(base_present)
+        self._check(lib().demi_replay_wildcard_candidates(self._h, m.ctypes.data if len(m) else None, len(m),
+                                                          bp.ctypes.data if bp is not None else None, d.ctypes.data if len(d) else None,
+                                                          len(d), C.byref(limits), out.ctypes.data if len(m) else None,
+                                                          plane.ctypes.data if want_all and len(m) else None))
+        return (out, plane) if want_all else out
+
+    def wildcard_ddmin(self, limits, drops, params=None, conjoined=None, base_present=None, cap=4096):
+        """RunnerUtils.wildcardDDMin on the loaded replay and selectors, natively (demi_wildcard_ddmin): (mcs indices,
+        [(candidate indices, passes, first_hit or None)] in consultation order, candidates per launch, stats, result)."""
+        import numpy as np
+        params = params or T.DdminParams(check_unmodified=0)
+        mcs = np.zeros(4, dtype=np.uint64)
+        consulted = np.zeros((cap, 4), dtype=np.uint64)
+        passed = np.zeros(cap, dtype=np.uint8)
+        hits = np.zeros(cap, dtype=np.uint32)
+        batches = np.zeros(cap, dtype=np.uint32)
+        st, res = T.DdminStats(), T.WildcardDdminResult()
+        d = np.ascontiguousarray(drops, dtype=np.uint32).reshape(-1)
+        conj = np.ascontiguousarray(conjoined, dtype=np.uint8) if conjoined is not None else None
+        bp = self._base_present(base_present)
+        self._check(lib().demi_wildcard_ddmin(self._h, C.byref(limits), C.byref(params), conj.ctypes.data if conj is not None else None,
+                                              bp.ctypes.data if bp is not None else None, d.ctypes.data if len(d) else None, len(d),
+                                              mcs.ctypes.data, consulted.ctypes.data, passed.ctypes.data, hits.ctypes.data, cap,
+                                              batches.ctypes.data, cap, C.byref(st), C.byref(res)))
+        cons = [(T.mask_to_events(consulted[i]), bool(passed[i]), None if int(hits[i]) == T.NO_HIT else int(hits[i]))
+                for i in range(min(cap, st.consultations))]
+        return T.mask_to_events(mcs), cons, [int(b) for b in batches[:min(cap, st.launches)]], st, res
 
     def dpor_load(self, externals, areas=None):
         import numpy as np

@@ -365,17 +365,18 @@ class SpeculativeDdmin {
 };
 
 // RunnerUtils.stsSchedDDMin (:642-707): WaitQuiescence stripped from the externals, DDMin over the replay oracle, the MCS
-// verified.  out_consulted / out_passed (may be NULL) receive the first `cap` consultations.
+// verified.  out_consulted / out_passed (may be NULL) receive the first `cap` consultations.  RunnerUtils.wildcardDDMin
+// (:709-767) is the same walk over another oracle (demi_wildcard_ddmin); `sequential`: one consultation per launch.
 template <class TestBatch>
 int sts_sched_ddmin(const demi_ext_event* ext, uint32_t n_ext, const uint8_t* conjoined, const demi_ddmin_params* par, TestBatch&& test,
                     uint64_t out_mcs[4], uint64_t* out_consulted, uint8_t* out_passed, uint32_t cap, uint32_t* out_batches,
-                    uint32_t batches_cap, demi_ddmin_stats* stats) {
+                    uint32_t batches_cap, demi_ddmin_stats* stats, bool sequential = false, DdminOutcome* keep = nullptr) {
   memset(stats, 0, sizeof *stats);
   DdminDag dag(ext, n_ext, conjoined);
   Mask256 view;
   for (uint32_t i = 0; i < n_ext; i++) if (ext[i].kind != DEMI_EV_WAIT_QUIESCENCE) view.set(i);
   DdminOutcome o;
-  SpeculativeDdmin<typename std::remove_reference<TestBatch>::type> dd(dag, test, par->depth, par->max_candidates);
+  SpeculativeDdmin<typename std::remove_reference<TestBatch>::type> dd(dag, test, par->depth, par->max_candidates, sequential);
   const double t0 = std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
   int rc = dd.minimize(view, par->check_unmodified != 0, par->verify_mcs != 0, &o);
   if (demi_host::knob("DEMI_DDMIN_TIMING")) {
@@ -384,6 +385,7 @@ int sts_sched_ddmin(const demi_ext_event* ext, uint32_t n_ext, const uint8_t* co
             (unsigned long long)o.replays, dd.oracle_s_ * 1e3, (t1 - t0 - dd.oracle_s_) * 1e3);
   }
   stats->consultations = o.consultations; stats->launches = o.launches; stats->replays = o.replays;
+  if (keep) *keep = o;               // (an oracle that knows more about a candidate than pass / fail looks its consultations up)
   if (rc) return rc;
   for (int k = 0; k < 4; k++) out_mcs[k] = o.mcs.w[k];
   stats->mcs_len = o.mcs.count();

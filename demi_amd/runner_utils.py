@@ -8,6 +8,7 @@ import numpy as np
 
 from . import types as T
 from .incremental_ddmin import dpor_initial_trace
+from .minification import SpeculativeDDMin
 from .provenance import pruneConcurrentEvents
 from .schedulers import (EventTrace, FullyRandom, MinimizationStats, RandomScheduler, ReplayException, ReplayScheduler,
                          SchedulerConfig, ViolationFingerprint)
@@ -77,11 +78,109 @@ def fuzz(generateFuzzTest: Callable[[int], np.ndarray], schedulerConfig: Schedul
     return None
 
 
+def wildcardDDMin(schedulerConfig: SchedulerConfig, originalTrace: EventTrace, violation: ViolationFingerprint,
+                  resolutionStrategy=None, stats: Optional[MinimizationStats] = None, native: bool = False, speculative_depth: int = 0,
+                  max_candidates: int = 0, sequential: bool = False, oracle=None, device: int = 0, p_max: int = 64):
+    """RunnerUtils.wildcardDDMin (RunnerUtils.scala:709-767) with TestScheduler.STSSched: DDMin over the externals of
+    originalTrace (WaitQuiescence stripped, as runTheGamut hands them over, :370-378) whose oracle is WildcardTestOracle.
+    Returns what the Scala returns - (externals of the MCS as indices into originalTrace.original_externals, stats, validated
+    trace, violation) - and, fifth, the DDMin record (consulted, first_hits, batches).
+
+    Two modes that agree on the MCS, the consultations, their first_hits, stats.total_replays and the validated trace:
+    native=False walks the decision tree here over replay_wildcard_candidates (speculative_depth levels ahead per launch;
+    sequential=True, or speculative_depth = 0 with a stand-in oracle, consults one candidate at a time), native=True makes the
+    one call demi_wildcard_ddmin (depth / max_candidates as in demi_ddmin_params; sequential = one consultation per launch).
+    `oracle`: a stand-in for StsWildcardOracle (tests)."""
+    from . import wildcard_minimization as W
+    from .minification import DDMin, EventDagView, UnmodifiedEventDag
+    stats = stats if stats is not None else MinimizationStats()
+    externals = originalTrace.original_externals
+    wo = W.WildcardTestOracle(schedulerConfig, originalTrace, resolutionStrategy=resolutionStrategy, oracle=oracle, device=device,
+                              p_max=p_max)
+    try:
+        dag = UnmodifiedEventDag(externals)
+        keep = tuple(i for i in dag.events if int(externals[i]["kind"]) != T.EV_WAIT_QUIESCENCE)
+        if native:
+            par = T.DdminParams(depth=1 if sequential else speculative_depth, max_candidates=1 if sequential else max_candidates,
+                                check_unmodified=0, verify_mcs=1)
+            mcs, consulted, batches, st, res = wo.oracle._ctx.wildcard_ddmin(wo.oracle._limits(violation), wo.drops, params=par)
+            stats.total_replays = int(res.total_replays)
+            record = _WildcardDdminRecord([(c, p) for c, p, _ in consulted], [h for _, _, h in consulted], batches, st, res)
+            wo.violation = violation
+            if len(mcs) < len(keep):
+                if st.verified:
+                    validated = wo.executed_trace(mcs, int(res.mcs_first_hit), violation)
+                else:       # the stop-gap of :752-758: the smallest trace a consultation reproduced, as the native call kept it
+                    if int(res.min_first_hit) == T.NO_HIT:
+                        return (), stats, originalTrace, violation, record
+                    ext = tuple(T.mask_to_events(np.array(list(res.min_externals), dtype=np.uint64)))
+                    return ext, stats, wo.executed_trace(ext, int(res.min_first_hit), violation), violation, record
+                return tuple(mcs), stats, validated, violation, record
+            return tuple(mcs), stats, originalTrace, violation, record
+        if sequential or not speculative_depth:
+            ddmin = DDMin(_FetchlessOracle(wo), checkUnmodifed=False, stats=stats)
+        else:
+            ddmin = _WildcardSpeculativeDDMin(wo, depth=speculative_depth, checkUnmodifed=False, stats=stats)
+        mcs = ddmin.minimize(EventDagView(dag, keep), violation)
+        record = _WildcardDdminRecord(ddmin.consulted, list(wo.first_hits), list(getattr(ddmin, "batches", [])), None, None)
+        if mcs.length < len(keep):
+            validated = wo.test(mcs.events, violation, MinimizationStats())            # ddmin.verify_mcs
+            if validated is None:
+                return wo.externalsForMinTrace, stats, wo.minTrace, violation, record
+            return tuple(mcs.events), stats, validated, violation, record
+        return tuple(mcs.events), stats, originalTrace, violation, record
+    finally:
+        wo.shutdown()
+
+
+class _FetchlessOracle:
+    """DDMin only asks whether test() is None: the executed trace of a consultation is not fetched."""
+
+    def __init__(self, wo):
+        self.wo = wo
+
+    def test(self, events, violation, stats=None):
+        return self.wo.test(events, violation, stats, fetch=False)
+
+
+class _WildcardDdminRecord:
+    """consulted [(candidate indices, passes)], first_hits [int or None] in consultation order, candidates per launch; the
+    native call's demi_ddmin_stats / demi_wildcard_ddmin_result (None for the mirror's walk)."""
+
+    def __init__(self, consulted, first_hits, batches, st, res):
+        self.consulted = [(tuple(int(i) for i in c), bool(p)) for c, p in consulted]
+        self.first_hits = list(first_hits)
+        self.batches = list(batches)
+        self.stats, self.result = st, res
+
+
+class _WildcardSpeculativeDDMin(SpeculativeDDMin):
+    """SpeculativeDDMin whose consultations are WildcardTestOracle's: the frontier's candidates are evaluated in one launch,
+    and the consultation itself does the oracle's bookkeeping (first_hit + 1 or 1 + T replays, minTrace)."""
+
+    def _passes(self, events):
+        events = tuple(events)
+        if events not in self.oracle.records:
+            todo = {events: None}
+            self._frontier(*self._node, self.depth, todo)
+            cands = [c for c in todo if c not in self.oracle.records]
+            results = self.oracle.test_batch(cands, self.violation_fingerprint, None)
+            self.speculative_replays += len(cands) * (1 + len(self.oracle.drops))
+            self.batches.append(len(cands))
+            for c, reproduced in zip(cands, results):
+                self.cache[c] = not reproduced
+        passes = self.oracle.test(events, self.violation_fingerprint, self._stats, fetch=False) is None
+        self.consulted.append((events, passes))
+        return passes
+
+
 def run_the_gamut(schedulerConfig: SchedulerConfig, trace: EventTrace, violation: ViolationFingerprint,
-                  stages: Sequence[str] = ("DDMin", "IntMin"), device: int = 0, p_max: int = 64):
+                  stages: Sequence[str] = ("DDMin", "IntMin"), device: int = 0, p_max: int = 64,
+                  shouldRerunDDMin: Callable[[np.ndarray], bool] = lambda externals: True):
     """The stages of RunnerUtils.runTheGamut (:165-380) that run on the GPU path, in the reference's order:
     stsSchedDDMin (external events), then minimizeInternals with LeftToRightOneAtATime, then - only when named in `stages` -
-    "WildcardsNoBackTracks" and "WildcardsLastOnly" (wildcard_minimization.WildcardMinimizer, ClockClusterizer).  Returns a dict with the MCS
+    "WildCardDDMinNoBacktracks" and "WildCardDDMinLastOnly" (wildcardDDMin over the current trace, :363-411, guarded by
+    shouldRerunDDMin as there), then "WildcardsNoBackTracks" and "WildcardsLastOnly" (wildcard_minimization.WildcardMinimizer, ClockClusterizer).  Returns a dict with the MCS
     (indices into trace.original_externals), the verified MCS execution, the internally minimized execution and the
     replay counts of each stage."""
     from .internal_minimization import countMsgEvents, minimizeInternals
@@ -106,6 +205,20 @@ def run_the_gamut(schedulerConfig: SchedulerConfig, trace: EventTrace, violation
                                          device=device, p_max=p_max)
         out.update(intmin_replays=stats.total_replays, minimized=minimized, minimized_deliveries=countMsgEvents(minimized))
         cur_trace = minimized
+    # wildcard DDMin over the externals, opt-in, as RunnerUtils.scala:363-411 places and configures it: without backtracks (the
+    # default strategy), then with LastOnlyStrategy
+    for stage, strategy in (("WildCardDDMinNoBacktracks", None), ("WildCardDDMinLastOnly", "LastOnlyStrategy")):
+        if stage in stages and cur_trace is not None and shouldRerunDDMin(cur_trace.original_externals):
+            from . import wildcard_minimization as W
+            stats = MinimizationStats()
+            ext, _, validated, _, _ = wildcardDDMin(schedulerConfig, cur_trace, violation, native=True, stats=stats,
+                                                    resolutionStrategy=getattr(W, strategy)() if strategy else None,
+                                                    device=device, p_max=p_max)
+            out.setdefault("wildcard_ddmin_replays", {})[stage] = stats.total_replays
+            out.setdefault("wildcard_ddmin_externals", {})[stage] = len(ext)
+            if validated is not None:
+                cur_trace = validated
+                out.update(wildcard_ddmin_trace=cur_trace)
     # the wildcard (fungible-clock) stages, opt-in, as RunnerUtils.scala:412-440 configures them: STSSched as the oracle, the
     # default resolution strategy (BackTrackStrategy, its backtrack points no-ops) and then LastOnlyStrategy
     for stage, strategy in (("WildcardsNoBackTracks", None), ("WildcardsLastOnly", "LastOnlyStrategy")):

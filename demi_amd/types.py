@@ -135,6 +135,8 @@ def rec_area(e):
 
 FILTER_ABSENTS_OFF, FILTER_ABSENTS_LITERAL, FILTER_ABSENTS_CORRECTED = 0, 1, 2     # demi_filter_absents
 WILDCARD_HEAD, WILDCARD_FIRST, WILDCARD_LAST = 0, 1, 2     # demi_wildcard_policy
+WC_REPRODUCES, WC_UNKNOWN, WC_LONGER = 1, 2, 4             # demi_wildcard_candidate.flags (DEMI_WC_*)
+NO_HIT = 0xFFFFFFFF                                        # first_hit / first_ovf: none
 
 
 class Limits(C.Structure):
@@ -175,6 +177,13 @@ class DdminStats(C.Structure):
     """demi_ddmin_stats"""
     _fields_ = [("consultations", C.c_uint32), ("launches", C.c_uint32), ("mcs_len", C.c_uint32), ("verified", C.c_uint32),
                 ("replays", C.c_uint64)]
+
+
+class WildcardDdminResult(C.Structure):
+    """demi_wildcard_ddmin_result"""
+    _fields_ = [("total_replays", C.c_uint64), ("proposals_run", C.c_uint64), ("mcs_evaluated", C.c_uint32), ("mcs_first_hit", C.c_uint32),
+                ("mcs_executed_len", C.c_uint32), ("mcs_flags", C.c_uint32), ("retried", C.c_uint32), ("min_first_hit", C.c_uint32),
+                ("min_executed_len", C.c_uint32), ("reserved", C.c_uint32), ("min_externals", C.c_uint64 * 4)]
 
 
 class IncDdminParams(C.Structure):
@@ -235,6 +244,7 @@ assert C.sizeof(ExtEvent) == 8 and C.sizeof(Verdict) == 16 and C.sizeof(RecEvent
 import numpy as np  # noqa: E402
 
 VERDICT_DTYPE = np.dtype([("flags", "<u4"), ("fingerprint", "<u4"), ("hash", "<u8")])
+WILDCARD_CANDIDATE_DTYPE = np.dtype([("first_hit", "<u4"), ("executed_len", "<u4"), ("flags", "<u4"), ("first_ovf", "<u4"), ("hash", "<u8")])
 EXT_EVENT_DTYPE = np.dtype([("kind", "u1"), ("a", "u1"), ("b", "u1"), ("msg_type", "u1"),
                             ("p0", "u1"), ("p1", "u1"), ("p0_hi", "u1"), ("p1_hi", "u1")])
 REC_EVENT_DTYPE = np.dtype([("kind", "u1"), ("snd", "u1"), ("rcv", "u1"), ("msg_type", "u1"), ("p0", "<u2"), ("p1", "<u2"),
@@ -260,6 +270,7 @@ DPOR_TRACE_DTYPE = np.dtype([("key", "<u8"), ("word", "<u4"), ("parent", "u1"), 
 DPOR_PAIR_DTYPE = np.dtype([("branch", "u1"), ("later", "u1"), ("earlier", "u1"), ("pad", "u1")])
 assert DPOR_TRACE_DTYPE.itemsize == 16 and DPOR_PAIR_DTYPE.itemsize == 4
 VIOLATION_DTYPE = np.dtype([("index", "<u8"), ("fingerprint", "<u4"), ("flags", "<u4")])
+assert WILDCARD_CANDIDATE_DTYPE.itemsize == 24
 assert VERDICT_DTYPE.itemsize == 16 and VIOLATION_DTYPE.itemsize == 16 and EXT_EVENT_DTYPE.itemsize == 8 and REC_EVENT_DTYPE.itemsize == 16
 
 

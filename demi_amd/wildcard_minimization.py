@@ -336,29 +336,51 @@ class StsWildcardOracle:
         self._ctx.replay_wildcard_load(type_sets, policies)
         self._trace = trace
 
-    def test_batch(self, presents: Sequence[np.ndarray], violation: ViolationFingerprint) -> List[bool]:
+    def test_batch(self, presents: Sequence[np.ndarray], violation: ViolationFingerprint, masks=None) -> List[bool]:
+        """masks (uint64[n, 4], optional): the subsequence of the LOADED externals every candidate keeps - the trace stays
+        loaded with its own externals, so that the records' ext_idx stay aligned."""
         from .schedulers import CapacityExceeded, OVF_FLAGS
         presents = np.asarray(presents, dtype=bool).reshape(len(presents), -1)
+        if masks is not None:
+            masks = np.ascontiguousarray(masks, dtype=np.uint64).reshape(-1, 4)
         self.launches += 1
         self.batches.append(len(presents))
-        v = self._ctx.replay_wildcard_batch(presents, self._limits(violation))
+        v = self._ctx.replay_wildcard_batch(presents, self._limits(violation), masks=masks)
         bad = np.nonzero(v["flags"] & OVF_FLAGS)[0]
         if len(bad):      # a replay aborted on a capacity is no answer: repeat it with the largest pending set, else give up loudly
             self.launches += 1
-            v[bad] = self._ctx.replay_wildcard_batch(presents[bad], self._limits(violation, T.MAX_PENDING))
+            v[bad] = self._ctx.replay_wildcard_batch(presents[bad], self._limits(violation, T.MAX_PENDING),
+                                                     masks=None if masks is None else masks[bad])
             if (v["flags"] & OVF_FLAGS).any():
                 raise CapacityExceeded("a wildcard candidate's replay exceeds the engine's capacities")
         return [bool(f & T.V_VIOLATION) for f in v["flags"]]
 
-    def executed(self, present: np.ndarray, violation: ViolationFingerprint):
+    def test_candidates(self, masks, drops, violation: ViolationFingerprint, base_present=None) -> np.ndarray:
+        """One WildcardTestOracle.test per row of masks (demi_replay_wildcard_candidates): WILDCARD_CANDIDATE_DTYPE records.
+        A candidate that is unknown because of a capacity is evaluated again with the largest pending set."""
+        from .schedulers import CapacityExceeded
+        masks = np.ascontiguousarray(masks, dtype=np.uint64).reshape(-1, 4)
+        self.launches += 1
+        self.batches.append(len(masks))
+        r = self._ctx.replay_wildcard_candidates(masks, drops, self._limits(violation), base_present=base_present)
+        bad = np.nonzero(r["flags"] & T.WC_UNKNOWN)[0]
+        if len(bad):
+            self.launches += 1
+            self.retried = getattr(self, "retried", 0) + len(bad)
+            r[bad] = self._ctx.replay_wildcard_candidates(masks[bad], drops, self._limits(violation, T.MAX_PENDING), base_present=base_present)
+            if (r["flags"] & T.WC_UNKNOWN).any():
+                raise CapacityExceeded("a wildcard candidate's proposal exceeds the engine's capacities")
+        return r
+
+    def executed(self, present: np.ndarray, violation: ViolationFingerprint, mask=None):
         """test() of one candidate: (executed trace, record indices of the present deliveries that were ignored as absent)
-        iff it triggers the violation, else None."""
+        iff it triggers the violation, else None.  mask: as in test_batch."""
         from .schedulers import CapacityExceeded, OVF_FLAGS
         self.launches += 1
-        v, kept, rec = self._ctx.replay_wildcard_get_trace(present, self._limits(violation))
+        v, kept, rec = self._ctx.replay_wildcard_get_trace(present, self._limits(violation), mask=mask)
         if (int(v.flags) & OVF_FLAGS) and self.p_max < T.MAX_PENDING:
             self.launches += 1
-            v, kept, rec = self._ctx.replay_wildcard_get_trace(present, self._limits(violation, T.MAX_PENDING))
+            v, kept, rec = self._ctx.replay_wildcard_get_trace(present, self._limits(violation, T.MAX_PENDING), mask=mask)
         if int(v.flags) & OVF_FLAGS:
             raise CapacityExceeded("the replay exceeds the engine's capacities")
         if not (int(v.flags) & T.V_VIOLATION):
@@ -473,3 +495,101 @@ class WildcardMinimizer:
 def wildcardMinimize(schedulerConfig: SchedulerConfig, mcs: np.ndarray, trace: EventTrace, violation: ViolationFingerprint,
                      **kw) -> Tuple[MinimizationStats, EventTrace]:
     return WildcardMinimizer(schedulerConfig, mcs, trace, violation, **kw).minimize()
+
+
+# ------------------------------------------------------------------ WildcardTestOracle.scala
+class WildcardTestOracle:
+    """WildcardTestOracle.scala:11-61 with TestScheduler.STSSched: the TestOracle of RunnerUtils.wildcardDDMin.  test(events)
+    runs WildcardMinimizer(skipClockClusters = true) on the subsequence `events` of originalTrace's externals (indices into
+    originalTrace.original_externals).  Its ClockClusterizer (STOP_IMMEDIATELY) proposes the trace with every timer and then
+    the trace without the j-th timer in id order, and the minimizer stops at the first proposal that reproduces: the proposals
+    do not depend on each other's outcome, so a consultation - and a whole DDMin frontier of them - is one launch
+    (StsWildcardOracle.test_candidates, demi_replay_wildcard_candidates), reduced to (first_hit, executed length) per candidate.
+    `oracle`: a StsWildcardOracle or a stand-in with load / test_candidates / executed (created, and shut down, here when None)."""
+
+    def __init__(self, schedulerConfig: SchedulerConfig, originalTrace: EventTrace,
+                 resolutionStrategy: Optional[AmbiguityResolutionStrategy] = None, oracle=None, device: int = 0, p_max: int = 64):
+        self.schedulerConfig = schedulerConfig
+        self.originalTrace = originalTrace
+        self.resolutionStrategy = resolutionStrategy if resolutionStrategy is not None else BackTrackStrategy()
+        self._own = oracle is None
+        self.oracle = oracle if oracle is not None else StsWildcardOracle(schedulerConfig, device=device, p_max=p_max)
+        clusterizer = ClockClusterizer(originalTrace, schedulerConfig.model, self.resolutionStrategy,
+                                       aggressiveness=Aggressiveness.STOP_IMMEDIATELY, skipClockClusters=True)
+        d = clusterizer.d
+        # proposal 0: every delivery (the first clock cluster removes nothing); proposal j: without the j-th timer in id order
+        assert d.present(clusterizer.currentCluster | clusterizer.timerIterator.all)[d.idx].all()
+        self.drops = np.array([d.rec_of_id[i] for i in clusterizer.timerIterator.toRemove], dtype=np.uint32)
+        self.selectors = clusterizer.selectors()
+        self.oracle.load(originalTrace, *self.selectors)
+        self._min: Optional[Tuple[Tuple[int, ...], int, int]] = None      # (events, first_hit, executed length) of minTrace
+        self._min_trace: Optional[EventTrace] = None
+        self.records: Dict[Tuple[int, ...], np.void] = {}                # every candidate evaluated so far
+        self.first_hits: List[Optional[int]] = []                        # per test() call, in order
+        self.violation: Optional[ViolationFingerprint] = None
+
+    def getName(self) -> str:
+        return "WildcardTestOracle"
+
+    def present_of(self, first_hit: int) -> np.ndarray:
+        p = np.ones(len(self.originalTrace.events), dtype=bool)
+        if first_hit:
+            p[int(self.drops[first_hit - 1])] = False
+        return p
+
+    def evaluate(self, cands: Sequence[Sequence[int]], violation: ViolationFingerprint) -> List[np.void]:
+        from .minification import events_to_masks
+        cands = [tuple(int(e) for e in c) for c in cands]
+        todo = [c for c in dict.fromkeys(cands) if c not in self.records]
+        if todo:
+            r = self.oracle.test_candidates(events_to_masks(todo), self.drops, violation)
+            for c, x in zip(todo, r):
+                self.records[c] = x.copy()
+        return [self.records[c] for c in cands]
+
+    def test_batch(self, cands, violation: ViolationFingerprint, stats=None) -> List[bool]:
+        """Does test() answer Some(trace) for each candidate: reproduced, and not longer than the original (WildcardMinimizer.scala:217)."""
+        return [bool(int(r["flags"]) & T.WC_REPRODUCES) and not int(r["flags"]) & T.WC_LONGER for r in self.evaluate(cands, violation)]
+
+    def executed_trace(self, events: Sequence[int], first_hit: int, violation: ViolationFingerprint) -> EventTrace:
+        from .minification import events_to_mask
+        got = self.oracle.executed(self.present_of(first_hit), violation, mask=events_to_mask(tuple(events)))
+        assert got is not None, "the candidates launch and the single replay of the same proposal disagree"
+        ev = got[0].events.copy()                 # setOriginalExternalEvents(events): ext_idx renumbered to the subsequence
+        remap = np.full(256, 255, dtype=np.uint8)
+        remap[list(events)] = np.arange(len(events), dtype=np.uint8)
+        ev["ext_idx"] = remap[ev["ext_idx"]]
+        return EventTrace(ev, self.originalTrace.original_externals[list(events)].copy())
+
+    def test(self, events, violation: ViolationFingerprint, stats: Optional[MinimizationStats] = None, fetch: bool = True):
+        """Some(trace) / None as the Scala; fetch=False answers True in place of the trace (DDMin only asks whether it is None)."""
+        events = tuple(int(e) for e in events)
+        self.violation = violation
+        r = self.evaluate([events], violation)[0]
+        hit = bool(int(r["flags"]) & T.WC_REPRODUCES)
+        first_hit = int(r["first_hit"]) if hit else None
+        self.first_hits.append(first_hit)
+        if stats is not None:
+            stats.increment_replays(first_hit + 1 if hit else 1 + len(self.drops))
+        if not hit or int(r["flags"]) & T.WC_LONGER:
+            return None                                  # minimize() returned originalTrace itself
+        n = int(r["executed_len"])
+        if n < (self._min[2] if self._min is not None else len(self.originalTrace.events)):
+            self._min, self._min_trace = (events, first_hit, n), None
+        return self.executed_trace(events, first_hit, violation) if fetch else True
+
+    @property
+    def externalsForMinTrace(self) -> Tuple[int, ...]:
+        return self._min[0] if self._min is not None else ()
+
+    @property
+    def minTrace(self) -> EventTrace:
+        if self._min is None:
+            return self.originalTrace
+        if self._min_trace is None:
+            self._min_trace = self.executed_trace(self._min[0], self._min[1], self.violation)
+        return self._min_trace
+
+    def shutdown(self):
+        if self._own:
+            self.oracle.shutdown()

@@ -500,6 +500,44 @@ int demi_replay_wildcard_batch(demi_ctx* ctx, const uint64_t* masks /* [n][4] or
 int demi_replay_wildcard_get_trace(demi_ctx* ctx, const uint64_t* mask /* [4] or NULL */, const uint64_t* present /* [words] */,
                                    const demi_limits* limits, demi_verdict* verdict, uint8_t* kept, demi_rec_event* rec_out,
                                    uint32_t cap, uint32_t* n_out);
+/* One consultation of WildcardTestOracle.test (minification/wildcard_minimization/WildcardTestOracle.scala:33-61) per candidate:
+ * the wildcard counterpart of demi_random_explore_candidates.  A consultation runs WildcardMinimizer(skipClockClusters = true),
+ * whose ClockClusterizer (Aggressiveness.STOP_IMMEDIATELY) proposes the trace with every timer, then the trace without the
+ * first, the second, ... timer, and stops at the first proposal that reproduces the violation; the proposals do not depend on
+ * each other's outcome.  Here candidate c is the subsequence masks[c] of the loaded externals (as in demi_replay_batch),
+ * proposal 0 the presence row base_present (NULL: all ones) and proposal j >= 1 that row without the MsgEvent recorded at
+ * drops[j - 1]: ONE launch replays the n_cand x (1 + n_drop) work items with the semantics of demi_replay_wildcard_batch (same
+ * selectors, same verdict words; the presence rows are derived on the device) and reduces every candidate's proposals on the
+ * device.  out[c]:
+ *   first_hit     the smallest j whose replay has DEMI_V_VIOLATION and no capacity flag, 0xFFFFFFFF if none;
+ *   first_ovf     the smallest j whose replay was aborted on a capacity (DEMI_V_PENDING_OVF / DEMI_V_QUEUE_OVF), 0xFFFFFFFF if none;
+ *   flags         DEMI_WC_UNKNOWN iff first_ovf < first_hit - the sequential loop would have met the aborted replay first, so
+ *                 this is no answer (never "does not reproduce"): repeat with a larger limits->p_max.  Otherwise
+ *                 DEMI_WC_REPRODUCES iff there is a first_hit, and with it DEMI_WC_LONGER iff executed_len is larger than
+ *                 demi_replay_recorded_len: WildcardMinimizer.scala:217 (`ret.size <= minTrace.size`) then keeps the original
+ *                 trace and WildcardTestOracle.test answers None although the violation was reproduced;
+ *   executed_len  (with DEMI_WC_REPRODUCES) events of proposal first_hit's executed trace, hash: its verdict hash.
+ * LENGTH CONVENTION: executed_len is the length of what demi_replay_wildcard_get_trace returns for that proposal (applied
+ * external events, external MsgSends, every MsgEvent, the MsgSend of every DELIVERED internal or timer message), and it is
+ * compared with the loaded trace as it was given to demi_replay_load - traces this library records or returns
+ * (demi_random_get_trace after demi_replay_get_kept's projection, ..._wildcard_get_trace) are in that convention on both sides.
+ * out_all (may be NULL; for tests): the full plane, entry c * (1 + n_drop) + j = demi_replay_wildcard_batch's verdict of (c, j).
+ * DEMI_ERR_INVALID_ARG: limits->filter_known_absents != 0; a drops entry that is not a MsgEvent of the loaded trace. */
+#define DEMI_WC_REPRODUCES 0x1u
+#define DEMI_WC_UNKNOWN    0x2u
+#define DEMI_WC_LONGER     0x4u
+#define DEMI_WC_MAX_CANDIDATES 4096u   /* n_cand of one call (demi_ddmin_params.max_candidates' default); n_drop <= DEMI_MAX_REC_EVENTS */
+typedef struct {
+  uint32_t first_hit;
+  uint32_t executed_len;
+  uint32_t flags;        /* DEMI_WC_* */
+  uint32_t first_ovf;
+  uint64_t hash;
+} demi_wildcard_candidate;   /* 24 bytes */
+int demi_replay_wildcard_candidates(demi_ctx* ctx, const uint64_t* masks /* [n_cand][4] */, uint32_t n_cand,
+                                    const uint64_t* base_present /* [words] or NULL */, const uint32_t* drops /* [n_drop] */,
+                                    uint32_t n_drop, const demi_limits* limits, demi_wildcard_candidate* out /* [n_cand] */,
+                                    demi_verdict* out_all /* [n_cand * (1 + n_drop)] or NULL */);
 /* external events of the trace demi_trace_load holds (0: none) - what demi_random_ddmin's `conjoined` array must cover */
 uint32_t demi_trace_len(const demi_ctx* ctx);
 
@@ -538,6 +576,41 @@ typedef struct {
 int demi_ddmin(demi_ctx* ctx, const demi_limits* limits, const demi_ddmin_params* params, const uint8_t* conjoined,
                uint64_t out_mcs[4], uint64_t* out_consulted, uint8_t* out_passed, uint32_t cap, uint32_t* out_batches,
                uint32_t batches_cap, demi_ddmin_stats* stats);
+
+/* ---------------------------------------------------------- wildcardDDMin: DDMin over the wildcard replay oracle
+ * RunnerUtils.wildcardDDMin (RunnerUtils.scala:709-767) with TestScheduler.STSSched in one call: DDMin.minimize / ddmin2 over the
+ * loaded execution's externals - atoms, `conjoined`, split_list, params and outputs exactly as demi_ddmin - whose TestOracle is
+ * WildcardTestOracle.test: a candidate "fails" (still triggers the violation) iff demi_replay_wildcard_candidates reports
+ * DEMI_WC_REPRODUCES without DEMI_WC_LONGER for it.  demi_replay_wildcard_load must have loaded the selectors; base_present /
+ * drops / n_drop are that entry point's (the caller lists the clock-increment deliveries in id order).  The decision tree is
+ * evaluated speculatively, one candidates launch per frontier (max_candidates counts candidates, not proposals); depth = 1
+ * with max_candidates = 1 is the reference's loop: one consultation per launch, nothing cached.  The MCS, the consultation
+ * sequence and total_replays are the sequential algorithm's.  A DEMI_WC_UNKNOWN candidate is evaluated again with the largest
+ * pending set; DEMI_ERR_CAPACITY if it is still unknown.  out_first_hit [cap] (may be NULL): per consultation the first_hit
+ * (0xFFFFFFFF: no proposal reproduced).  stats->replays counts the proposals run on the device, speculation included.  The caller
+ * fetches the validated trace with demi_replay_wildcard_get_trace(mcs, base_present without drops[mcs_first_hit - 1]).
+ * DEMI_ERR_INVALID_ARG ("single rank") with a communicator attached: the frontiers are not sharded. */
+typedef struct {
+  uint64_t total_replays;     /* MinimizationStats.total_replays: per consultation first_hit + 1, or 1 + n_drop without a hit
+                                 (the STSScheduler.test calls of the reference's WildcardMinimizer) */
+  uint64_t proposals_run;     /* (candidate, proposal) replays on the device, speculation and retries included */
+  uint32_t mcs_evaluated;     /* the MCS itself was consulted or verified: the three fields below are its record */
+  uint32_t mcs_first_hit;     /* 0xFFFFFFFF: no proposal of the MCS reproduces */
+  uint32_t mcs_executed_len;
+  uint32_t mcs_flags;         /* DEMI_WC_* */
+  uint32_t retried;           /* candidates evaluated a second time with the largest pending set */
+  uint32_t min_first_hit;     /* WildcardTestOracle.minTrace / externalsForMinTrace (WildcardTestOracle.scala:53-57) after the last
+                                 consultation of the search: the first consultation with the shortest executed trace shorter than the
+                                 loaded one - its first_hit (0xFFFFFFFF: none, minTrace is the loaded trace), */
+  uint32_t min_executed_len;  /* its executed length */
+  uint32_t reserved;
+  uint64_t min_externals[4];  /* and its candidate, as a mask over the externals.  What :752-758 returns when the MCS does not verify. */
+} demi_wildcard_ddmin_result;
+int demi_wildcard_ddmin(demi_ctx* ctx, const demi_limits* limits, const demi_ddmin_params* params, const uint8_t* conjoined,
+                        const uint64_t* base_present /* [words] or NULL */, const uint32_t* drops /* [n_drop] */, uint32_t n_drop,
+                        uint64_t out_mcs[4], uint64_t* out_consulted /* [cap][4] or NULL */, uint8_t* out_passed /* [cap] or NULL */,
+                        uint32_t* out_first_hit /* [cap] or NULL */, uint32_t cap, uint32_t* out_batches, uint32_t batches_cap,
+                        demi_ddmin_stats* stats, demi_wildcard_ddmin_result* result);
 
 /* ---------------------------------------------------------- randomDDMin: DDMin over the RandomScheduler itself
  * RunnerUtils.randomDDMin (RunnerUtils.scala:601-623) in one call: DDMin (minification/DeltaDebugging.scala:27-109) whose

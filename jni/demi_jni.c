@@ -285,6 +285,152 @@ JNIEXPORT jint JNICALL FN(replayGetKept)(JNIEnv* e, jclass c, jlong h, jlongArra
   return rc;
 }
 
+/* ---- K2W: the replay oracle of the wildcard minimizers (demi_replay_wildcard_*).  typeSets: int[n recorded], policies: byte[n recorded]
+ *      (n = demi_replay_recorded_len of the execution replayLoad loaded; shorter arrays are refused) */
+JNIEXPORT jint JNICALL FN(replayWildcardLoad)(JNIEnv* e, jclass c, jlong h, jintArray typeSets, jbyteArray policies) {
+  (void)c;
+  const int64_t n_rec = (int64_t)demi_replay_recorded_len(CTX(h));
+  if (!typeSets || !policies || LEN(typeSets) < n_rec || LEN(policies) < n_rec) return DEMI_ERR_INVALID_ARG;
+  void* t = INTS(typeSets);
+  void* p = BYTES(policies);
+  jint rc = (LOST(typeSets, t) || LOST(policies, p)) ? DEMI_ERR_INVALID_ARG
+            : demi_replay_wildcard_load(CTX(h), (const uint32_t*)t, (const uint8_t*)p);
+  PUT_BYTES(policies, p, JNI_ABORT);
+  PUT_INTS(typeSets, t, JNI_ABORT);
+  return rc;
+}
+/* words of one presence row of the loaded execution: ceil(recorded events / 64) */
+static int64_t present_words(jlong h) { return ((int64_t)demi_replay_recorded_len(CTX(h)) + 63) / 64; }
+/* present: long[words * n] (n from verdicts: long[2 * n]); masksOrNull: long[4 * n] */
+JNIEXPORT jint JNICALL FN(replayWildcardBatch)(JNIEnv* e, jclass c, jlong h, jlongArray masksOrNull, jlongArray present, jintArray limits,
+                                              jlongArray verdicts) {
+  demi_limits lim;
+  (void)c;
+  if (limits_of(e, limits, &lim) || !present || LEN(verdicts) < 0 || LEN(verdicts) % 2) return DEMI_ERR_INVALID_ARG;
+  const int64_t n = LEN(verdicts) / 2, words = present_words(h);
+  if (LEN(present) < words * n || (masksOrNull && LEN(masksOrNull) < 4 * n)) return DEMI_ERR_INVALID_ARG;
+  void* m = LONGS(masksOrNull);
+  void* p = LONGS(present);
+  void* o = LONGS(verdicts);
+  jint rc = (LOST(masksOrNull, m) || LOST(present, p) || LOST(verdicts, o)) ? DEMI_ERR_INVALID_ARG
+            : demi_replay_wildcard_batch(CTX(h), (const uint64_t*)m, (const uint64_t*)p, (uint64_t)n, &lim, (demi_verdict*)o);
+  PUT_LONGS(verdicts, o, 0);
+  PUT_LONGS(present, p, JNI_ABORT);
+  PUT_LONGS(masksOrNull, m, JNI_ABORT);
+  return rc;
+}
+/* maskOrNull: long[4]; present: long[words]; verdict: long[2]; kept: byte[>= recorded events]; recorded: byte[16 * cap];
+ * returns the number of events of the executed trace, or a negative demi_status */
+JNIEXPORT jint JNICALL FN(replayWildcardGetTrace)(JNIEnv* e, jclass c, jlong h, jlongArray maskOrNull, jlongArray present, jintArray limits,
+                                                 jlongArray verdict, jbyteArray kept, jbyteArray recorded) {
+  demi_limits lim;
+  demi_verdict v;
+  (void)c;
+  if (limits_of(e, limits, &lim) || !present || LEN(present) < present_words(h) || LEN(verdict) != 2 || LEN(kept) < 0 ||
+      (maskOrNull && LEN(maskOrNull) != 4) || LEN(recorded) < 0 || LEN(recorded) % (jint)sizeof(demi_rec_event))
+    return DEMI_ERR_INVALID_ARG;
+  if ((uint64_t)LEN(kept) < (uint64_t)demi_replay_recorded_len(CTX(h))) return DEMI_ERR_CAPACITY;
+  const uint32_t cap = (uint32_t)(LEN(recorded) / (jint)sizeof(demi_rec_event));
+  uint32_t n_out = 0;
+  memset(&v, 0, sizeof v);
+  void* m = LONGS(maskOrNull);
+  void* p = LONGS(present);
+  void* k = BYTES(kept);
+  void* r = BYTES(recorded);
+  jint rc = (LOST(maskOrNull, m) || LOST(present, p) || LOST(kept, k) || LOST(recorded, r)) ? DEMI_ERR_INVALID_ARG
+            : demi_replay_wildcard_get_trace(CTX(h), (const uint64_t*)m, (const uint64_t*)p, &lim, &v, (uint8_t*)k, (demi_rec_event*)r, cap, &n_out);
+  PUT_BYTES(recorded, r, 0);
+  PUT_BYTES(kept, k, 0);
+  PUT_LONGS(present, p, JNI_ABORT);
+  PUT_LONGS(maskOrNull, m, JNI_ABORT);
+  SET_LONGS(verdict, 2, (const jlong*)(const void*)&v);
+  return rc == DEMI_OK ? (jint)n_out : rc;
+}
+/* ---- WildcardTestOracle.test per candidate (demi_replay_wildcard_candidates).  masks: long[4 * n]; basePresentOrNull: long[words];
+ *      drops: int[n_drop] (may be empty); out: long[3 * n] = demi_wildcard_candidate (first_hit | executed_len << 32, flags | first_ovf << 32,
+ *      hash); outAllOrNull: long[2 * n * (1 + n_drop)] */
+JNIEXPORT jint JNICALL FN(replayWildcardCandidates)(JNIEnv* e, jclass c, jlong h, jlongArray masks, jlongArray basePresentOrNull, jintArray drops,
+                                                   jintArray limits, jlongArray out, jlongArray outAllOrNull) {
+  demi_limits lim;
+  (void)c;
+  if (limits_of(e, limits, &lim) || !masks || LEN(masks) % 4 || !drops || !out) return DEMI_ERR_INVALID_ARG;
+  const int64_t n = LEN(masks) / 4, n_drop = LEN(drops);
+  if (LEN(out) < 3 * n || (basePresentOrNull && LEN(basePresentOrNull) < present_words(h)) ||
+      (outAllOrNull && LEN(outAllOrNull) < 2 * n * (n_drop + 1)))
+    return DEMI_ERR_INVALID_ARG;
+  void* m = LONGS(masks);
+  void* b = LONGS(basePresentOrNull);
+  void* d = INTS(drops);
+  void* o = LONGS(out);
+  void* a = LONGS(outAllOrNull);
+  jint rc = (LOST(masks, m) || LOST(basePresentOrNull, b) || LOST(drops, d) || LOST(out, o) || LOST(outAllOrNull, a)) ? DEMI_ERR_INVALID_ARG
+            : demi_replay_wildcard_candidates(CTX(h), (const uint64_t*)m, (uint32_t)n, (const uint64_t*)b, (const uint32_t*)d, (uint32_t)n_drop,
+                                              &lim, (demi_wildcard_candidate*)o, (demi_verdict*)a);
+  PUT_LONGS(outAllOrNull, a, 0);
+  PUT_LONGS(out, o, 0);
+  PUT_INTS(drops, d, JNI_ABORT);
+  PUT_LONGS(basePresentOrNull, b, JNI_ABORT);
+  PUT_LONGS(masks, m, JNI_ABORT);
+  return rc;
+}
+/* ---- RunnerUtils.wildcardDDMin in one call (demi_wildcard_ddmin).  params, conjoinedOrNull, mcs, consultedOrNull / passedOrNull, stats as
+ *      for ddmin; firstHitOrNull: int[cap] (with consultedOrNull; -1 = no proposal reproduced); result: long[13] = total_replays,
+ *      proposals_run, mcs_evaluated, mcs_first_hit (-1 = none), mcs_executed_len, mcs_flags, retried, min_first_hit (-1 = none),
+ *      min_executed_len, min_externals[4] */
+JNIEXPORT jint JNICALL FN(wildcardDDMin)(JNIEnv* e, jclass c, jlong h, jintArray limits, jintArray params, jbyteArray conjoinedOrNull,
+                                        jlongArray basePresentOrNull, jintArray drops, jlongArray mcs, jlongArray consultedOrNull,
+                                        jbyteArray passedOrNull, jintArray firstHitOrNull, jlongArray stats, jlongArray result) {
+  demi_limits lim;
+  demi_ddmin_params par;
+  demi_ddmin_stats st;
+  demi_wildcard_ddmin_result res;
+  jint pr[4];
+  uint64_t out[4] = {0, 0, 0, 0};
+  (void)c;
+  if (limits_of(e, limits, &lim) || LEN(params) != 4 || LEN(mcs) != 4 || LEN(stats) != 5 || LEN(result) != 13 || !drops) return DEMI_ERR_INVALID_ARG;
+  (*e)->GetIntArrayRegion(e, params, 0, 4, pr);
+  par.depth = (uint32_t)pr[0]; par.max_candidates = (uint32_t)pr[1]; par.check_unmodified = (uint32_t)pr[2]; par.verify_mcs = (uint32_t)pr[3];
+  if (conjoinedOrNull && LEN(conjoinedOrNull) < (int64_t)demi_replay_externals_len(CTX(h))) return DEMI_ERR_INVALID_ARG;
+  if (basePresentOrNull && LEN(basePresentOrNull) < present_words(h)) return DEMI_ERR_INVALID_ARG;
+  uint32_t cap = 0;
+  if (consultedOrNull) {
+    if (LEN(consultedOrNull) % 4 || !passedOrNull || LEN(passedOrNull) < LEN(consultedOrNull) / 4 ||
+        (firstHitOrNull && LEN(firstHitOrNull) < LEN(consultedOrNull) / 4))
+      return DEMI_ERR_INVALID_ARG;
+    cap = (uint32_t)(LEN(consultedOrNull) / 4);
+  }
+  memset(&st, 0, sizeof st);
+  memset(&res, 0, sizeof res);
+  const int64_t n_drop = LEN(drops);
+  void* cj = BYTES(conjoinedOrNull);
+  void* bp = LONGS(basePresentOrNull);
+  void* dr = INTS(drops);
+  void* co = LONGS(consultedOrNull);
+  void* pa = BYTES(passedOrNull);
+  void* fh = consultedOrNull ? INTS(firstHitOrNull) : NULL;
+  jint rc = (LOST(conjoinedOrNull, cj) || LOST(basePresentOrNull, bp) || LOST(drops, dr) || LOST(consultedOrNull, co) || LOST(passedOrNull, pa) ||
+             (consultedOrNull && LOST(firstHitOrNull, fh))) ? DEMI_ERR_INVALID_ARG
+            : demi_wildcard_ddmin(CTX(h), &lim, &par, (const uint8_t*)cj, (const uint64_t*)bp, (const uint32_t*)dr, (uint32_t)n_drop, out,
+                                  (uint64_t*)co, (uint8_t*)pa, (uint32_t*)fh, cap, NULL, 0, &st, &res);
+  if (consultedOrNull) PUT_INTS(firstHitOrNull, fh, 0);
+  PUT_BYTES(passedOrNull, pa, 0);
+  PUT_LONGS(consultedOrNull, co, 0);
+  PUT_INTS(drops, dr, JNI_ABORT);
+  PUT_LONGS(basePresentOrNull, bp, JNI_ABORT);
+  PUT_BYTES(conjoinedOrNull, cj, JNI_ABORT);
+  SET_LONGS(mcs, 4, (const jlong*)(const void*)out);
+  jlong o[5];
+  o[0] = (jlong)st.consultations; o[1] = (jlong)st.launches; o[2] = (jlong)st.mcs_len; o[3] = (jlong)st.verified; o[4] = (jlong)st.replays;
+  SET_LONGS(stats, 5, o);
+  jlong r[13];
+  r[0] = (jlong)res.total_replays; r[1] = (jlong)res.proposals_run; r[2] = (jlong)res.mcs_evaluated; r[3] = (jlong)(int32_t)res.mcs_first_hit;
+  r[4] = (jlong)res.mcs_executed_len; r[5] = (jlong)res.mcs_flags; r[6] = (jlong)res.retried;
+  r[7] = (jlong)(int32_t)res.min_first_hit; r[8] = (jlong)res.min_executed_len;
+  for (int i = 0; i < 4; i++) r[9 + i] = (jlong)res.min_externals[i];
+  SET_LONGS(result, 13, r);
+  return rc;
+}
+
 /* ---- DDMin in one call (demi_ddmin).  params: int[4] (demi_ddmin_params); conjoinedOrNull: byte[>= n externals of replayLoad]; mcs: long[4];
  *      consultedOrNull: long[4 * cap] with passedOrNull: byte[cap]; stats: long[5] = consultations, launches, mcs_len, verified, replays */
 JNIEXPORT jint JNICALL FN(ddmin)(JNIEnv* e, jclass c, jlong h, jintArray limits, jintArray params, jbyteArray conjoinedOrNull, jlongArray mcs,

@@ -9,6 +9,7 @@ object DemiGpu {
   val V_VIOLATION = 0x1; val V_MAXMSG = 0x2; val V_PENDING_OVF = 0x4; val V_QUEUE_OVF = 0x8; val V_DIVERGED = 0x10
   val V_TRACE_OVF = 0x20; val V_PAIRS_OVF = 0x40; val V_SELFMSG = 0x80
   val MAX_PENDING = 128
+  val MAX_REC_EVENTS = 16384
   val DPOR_ORDER_ROUNDS = 0; val DPOR_ORDER_REFERENCE = 1
 
   @native def ctxCreate(device: Int): Long
@@ -49,6 +50,30 @@ object DemiGpu {
   @native def randomExploreCandidates(h: Long, seedBase: Long, masks: Array[Long], executions: Int, limits: Array[Int],
                                       verdictsOrNull: Array[Long], flags: Array[Int]): Int
   @native def replayGetKept(h: Long, maskOrNull: Array[Long], skip: Int, limits: Array[Int], verdict: Array[Long], kept: Array[Byte]): Int
+  /** the selectors of the execution replayLoad loaded (demi_replay_wildcard_load): typeSets = int[n recorded] (bit t = message type t
+   *  matches, 0 = exact delivery), policies = byte[n recorded] (0 HEAD = SrcDstFIFOOnly, 1 FIRST = BackTrackStrategy / the timer wildcard,
+   *  2 LAST = LastOnlyStrategy) */
+  @native def replayWildcardLoad(h: Long, typeSets: Array[Int], policies: Array[Byte]): Int
+  /** one STSScheduler.test of a wildcarded trace per row (demi_replay_wildcard_batch): present = long[ceil(n recorded / 64) * n],
+   *  bit i of a row = the MsgEvent recorded at i is part of the trace; verdicts = long[2 * n] */
+  @native def replayWildcardBatch(h: Long, masksOrNull: Array[Long], present: Array[Long], limits: Array[Int], verdicts: Array[Long]): Int
+  /** one candidate once more, recorded (demi_replay_wildcard_get_trace): returns the number of events of the executed trace in
+   *  `recorded` (16 bytes each), or a negative status; kept = byte[n recorded] */
+  @native def replayWildcardGetTrace(h: Long, maskOrNull: Array[Long], present: Array[Long], limits: Array[Int], verdict: Array[Long],
+                                     kept: Array[Byte], recorded: Array[Byte]): Int
+  /** one WildcardTestOracle.test per candidate (demi_replay_wildcard_candidates): masks = long[4 * n]; proposal 0 = basePresentOrNull
+   *  (null: every delivery), proposal j = that row without the MsgEvent recorded at drops(j - 1); out = long[3 * n]
+   *  (first_hit | executed_len << 32, flags | first_ovf << 32, hash; flags: 1 reproduces, 2 unknown because of a capacity, 4 longer than
+   *  the loaded trace); outAllOrNull = long[2 * n * (1 + drops.length)] */
+  @native def replayWildcardCandidates(h: Long, masks: Array[Long], basePresentOrNull: Array[Long], drops: Array[Int], limits: Array[Int],
+                                       out: Array[Long], outAllOrNull: Array[Long]): Int
+  /** RunnerUtils.wildcardDDMin in one call (demi_wildcard_ddmin): params, conjoinedOrNull, mcs, consultedOrNull / passedOrNull and stats as
+   *  for ddmin; firstHitOrNull = int[cap] (-1: no proposal reproduced); result = long[13] (total_replays, proposals_run, mcs_evaluated,
+   *  mcs_first_hit (-1: none), mcs_executed_len, mcs_flags, retried, min_first_hit (-1: none), min_executed_len, min_externals[4]:
+   *  WildcardTestOracle's minTrace / externalsForMinTrace after the search) */
+  @native def wildcardDDMin(h: Long, limits: Array[Int], params: Array[Int], conjoinedOrNull: Array[Byte], basePresentOrNull: Array[Long],
+                            drops: Array[Int], mcs: Array[Long], consultedOrNull: Array[Long], passedOrNull: Array[Byte],
+                            firstHitOrNull: Array[Int], stats: Array[Long], result: Array[Long]): Int
   @native def dporLoad(h: Long, externals: Array[Byte]): Int
   /** returns the length of the first violating trace (entries of 16 bytes in firstViolationTrace), or a negative status */
   /** ArvindDistanceOrdering.init(sched, originalTrace) / setInitialTrace for the following dporExplore calls (node keys; 16-byte trace entries) */

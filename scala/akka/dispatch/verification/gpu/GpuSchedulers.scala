@@ -466,6 +466,84 @@ object GpuRandomDDMin {
   }
 }
 
+/** RunnerUtils.wildcardDDMin (RunnerUtils.scala:709-767) with TestScheduler.STSSched in ONE native call (demi_wildcard_ddmin): DDMin over
+ *  the externals of `originalTrace` whose oracle is WildcardTestOracle.test - WildcardMinimizer(skipClockClusters = true), whose
+ *  ClockClusterizer proposes the trace with every timer and then the trace without the first, the second, ... timer in id order.  The
+ *  decision tree, the speculative frontiers and their launches - (candidates x (1 + timers)) replays each - run inside the library.
+ *  `dag` is what runTheGamut hands over: the externals without WaitQuiescence / WaitCondition (:370-378; the library strips
+ *  WaitQuiescence itself).  Returns what the reference returns: (mcs externals, stats, Some(validated trace) - the original trace when
+ *  nothing was removed -, the violation); stats counts first_hit + 1 replays per consultation, 1 + timers where nothing reproduced.
+ *  resolutionStrategy: null = BackTrackStrategy, as in the reference.  Where the MCS does not verify, the smallest trace a
+ *  consultation reproduced and its externals are returned, as :752-758 does (the library keeps oracle.minTrace's candidate). */
+object GpuWildcardDDMin {
+  def apply(schedulerConfig: SchedulerConfig, lowering: TableLowering, originalTrace: EventTrace, violation: ViolationFingerprint,
+            resolutionStrategy: AmbiguityResolutionStrategy = null, stats: Option[MinimizationStats] = None, device: Int = 0,
+            pMax: Int = 64, maxCandidates: Int = 0): (Seq[ExternalEvent], MinimizationStats, Option[EventTrace], ViolationFingerprint) = {
+    if (schedulerConfig.invariant_check.isEmpty) throw new IllegalArgumentException("Must invoke setInvariant before test()")
+    if (schedulerConfig.filterKnownAbsents) throw new UnsupportedOnGpu("the wildcard replay with filterKnownAbsents")
+    val h = ctxCreate(device)
+    if (h == 0) throw new IllegalStateException("no MI355X visible: use RunnerUtils.wildcardDDMin")
+    try {
+      val m = lowering.model
+      check(h, modelLoad(h, m.nActors, m.msgClass, m.actorClass, m.nClasses, m.handlerStart, m.code, m.initState,
+                         Array(m.invKind, m.invFa, m.invVa, m.invFb, m.fpMatchMask, m.flags)))
+      if (m.compiledOnly) check(h, modelSpecialize(h, true)) else modelSpecialize(h, true)
+      val ext = originalTrace.original_externals
+      check(h, replayLoad(h, FlatEvents.pack(ext, lowering), FlatEvents.packRecorded(originalTrace, lowering)))
+      // ClockClusterizer's selectors (ClockClusterizer.scala:100-128): external deliveries stay exact, a timer (causesClockIncrement)
+      // matches any clock-increment type with the first match, every other delivery its own class tag under the resolution strategy
+      val fingerprinter = schedulerConfig.messageFingerprinter
+      val policy: Byte = resolutionStrategy match {
+        case _: SrcDstFIFOOnly => 0
+        case _: LastOnlyStrategy => 2
+        case _ => 1
+      }
+      val events = originalTrace.events.toIndexedSeq
+      val typeSets = new Array[Int](events.size); val policies = new Array[Byte](events.size)
+      val timers = new scala.collection.mutable.ArrayBuffer[(Int, Int)]()          // (Uniq id, recorded index)
+      var incTypes = 0
+      for ((e, i) <- events.zipWithIndex) e match {
+        case UniqueMsgEvent(MsgEvent(_, _, msg), id) if !EventTypes.isExternal(e) && fingerprinter.causesClockIncrement(msg) =>
+          incTypes |= 1 << lowering.encodeFields(msg)._1; timers += ((id, i))
+        case _ =>
+      }
+      for ((e, i) <- events.zipWithIndex) e match {
+        case UniqueMsgEvent(MsgEvent(_, _, msg), _) if !EventTypes.isExternal(e) =>
+          if (fingerprinter.causesClockIncrement(msg)) { typeSets(i) = incTypes; policies(i) = 1 }
+          else { typeSets(i) = 1 << lowering.encodeFields(msg)._1; policies(i) = policy }
+        case _ =>
+      }
+      check(h, replayWildcardLoad(h, typeSets, policies))
+      val drops = timers.sortBy(_._1).map(_._2).toArray                           // OneAtATimeIterator: the timers in id order
+      val limits = Array(0, 0, pMax, 1, lowering.fingerprintCode(violation), 0, 0, 0, 1)
+      val mcs = new Array[Long](4); val st = new Array[Long](5); val res = new Array[Long](13)
+      check(h, DemiGpu.wildcardDDMin(h, limits, Array(0, maxCandidates, 0 /* DDMin(oracle): checkUnmodifed = false */, 1), null, null, drops,
+                                     mcs, null, null, null, st, res))
+      val out = stats.getOrElse(new MinimizationStats)
+      (0L until res(0)).foreach(_ => out.increment_replays())
+      val kept = ext.indices.filter(i => ((mcs(i >> 6) >>> (i & 63)) & 1L) != 0).map(ext)
+      val externalsSize = ext.count { case WaitQuiescence() => false; case WaitCondition(_) => false; case _ => true }
+      def subseq(mask: Array[Long]) = ext.indices.filter(i => ((mask(i >> 6) >>> (i & 63)) & 1L) != 0)
+      // the executed trace of proposal `hit` of the candidate `mask`, re-based on it (setOriginalExternalEvents, :747 / :755)
+      def executed(mask: Array[Long], hit: Int): EventTrace = {
+        val present = Array.fill(math.max((events.size + 63) / 64, 1))(-1L)
+        if (hit > 0) { val d = drops(hit - 1); present(d >> 6) &= ~(1L << (d & 63)) }
+        val v = new Array[Long](2); val k = new Array[Byte](events.size); val rec = new Array[Byte](16 * MAX_REC_EVENTS)
+        val big = limits.clone; big(2) = MAX_PENDING
+        val n = replayWildcardGetTrace(h, mask, present, big, v, k, rec)
+        check(h, math.min(n, 0))
+        val index = subseq(mask).zipWithIndex.toMap
+        for (i <- 0 until n) { val x = rec(16 * i + 9) & 0xFF; if (x != 255) rec(16 * i + 9) = index(x).toByte }
+        FlatEvents.toEventTrace(rec, n, subseq(mask).map(ext), lowering)
+      }
+      if (kept.size >= externalsSize) (kept, out, Some(originalTrace), violation)
+      else if (st(3) == 1L) (kept, out, Some(executed(mcs, res(3).toInt)), violation)
+      else if (res(7) < 0) (Seq.empty, out, Some(originalTrace), violation)       // (:752-758 with oracle.minTrace still the original)
+      else { val min = res.slice(9, 13); (subseq(min).map(ext), out, Some(executed(min, res(7).toInt)), violation) }
+    } finally ctxDestroy(h)
+  }
+}
+
 object GpuDPOR {
   /** demi_dpor_trace_entry[] (key 8, word 4, parent, qperiod, depth, kind) -> the MsgEvents of the violating interleaving */
   def traceOf(vt: Array[Byte], n: Int, externals: Seq[ExternalEvent], lo: TableLowering): EventTrace = {
