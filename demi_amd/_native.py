@@ -19,7 +19,8 @@ EXPORTS = ["demi_ctx_create", "demi_ctx_destroy", "demi_last_error", "demi_versi
            "demi_comm_unique_id", "demi_comm_create", "demi_comm_create_host", "demi_comm_destroy", "demi_comm_rank",
            "demi_comm_allgather_dev", "demi_random_explore_sharded", "demi_replay_batch_sharded", "demi_abi_version", "demi_replay_externals_len", "demi_edit_distance_dpor_ddmin", "demi_dpor_explored", "demi_random_ddmin", "demi_random_explore_candidates", "demi_ext_payload_areas",
            "demi_replay_wildcard_load", "demi_replay_wildcard_batch", "demi_replay_wildcard_get_trace",
-           "demi_replay_wildcard_candidates", "demi_wildcard_ddmin"]
+           "demi_replay_wildcard_candidates", "demi_wildcard_ddmin",
+           "demi_fuzz_stride", "demi_fuzz_generate", "demi_random_explore_tests", "demi_fuzz_campaign"]
 
 _lib = None
 ALLGATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t)     # demi_allgather_fn
@@ -141,6 +142,13 @@ def lib():
     L.demi_provenance_prune.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p]
     L.demi_device_probe_mix.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(T.ProbeResult)]
     L.demi_calib_rw.argtypes = [C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint32]
+    L.demi_fuzz_stride.argtypes = [C.POINTER(T.FuzzParams)]
+    L.demi_fuzz_stride.restype = C.c_uint32
+    L.demi_fuzz_generate.argtypes = [C.c_void_p, C.POINTER(T.FuzzParams), C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.demi_random_explore_tests.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(T.Limits),
+                                            C.c_void_p, C.c_void_p]
+    L.demi_fuzz_campaign.argtypes = [C.c_void_p, C.POINTER(T.FuzzParams), C.POINTER(T.FuzzCampaignParams), C.POINTER(T.Limits), C.c_void_p,
+                                     C.c_uint32, C.POINTER(T.FuzzCampaignResult)]
     # every export has its argument types declared: an undeclared one would silently truncate pointers to 32 bits
     for name in EXPORTS:
         fn = getattr(L, name)
@@ -347,6 +355,91 @@ class Context:
         self._check(lib().demi_random_explore_candidates(self._h, C.c_uint64(seed_base), m.ctypes.data, len(m), executions, C.byref(limits),
                                                          v.ctypes.data, f.ctypes.data))
         return v, f
+
+    @staticmethod
+    def fuzz_params(num_events, weights, send_gen, prefix, postfix=()):
+        """demi_fuzz_params for Fuzzer(num_events, weights, send_gen, prefix, postfix): (struct, the arrays it points into - keep
+        them alive as long as the struct).  send_gen: fuzzer.SendGenerator; prefix / postfix: event tuples or EXT_EVENT_DTYPE."""
+        import numpy as np
+        from . import fuzzer as F
+
+        def arr(ev):
+            if isinstance(ev, np.ndarray):
+                return np.ascontiguousarray(ev, dtype=T.EXT_EVENT_DTYPE)
+            return F.events_to_array(list(ev))
+        pre, post = arr(prefix), arr(postfix)
+        par = T.FuzzParams()
+        par.num_events, par.n_prefix, par.n_postfix = num_events, len(pre), len(post)
+        par.prefix = pre.ctypes.data if len(pre) else None
+        par.postfix = post.ctypes.data if len(post) else None
+        total, *cum = F.fuzz_thresholds(weights)
+        par.total_mass = total
+        for i in range(4):
+            par.cum[i] = cum[i]
+        C.memmove(C.byref(par.gen), send_gen.to_struct().ctypes.data, C.sizeof(T.FuzzSendGen))
+        return par, (pre, post)
+
+    def fuzz_generate(self, n_tests, num_events, weights, send_gen, prefix, postfix=(), seed_base=0, seeds=None, copy_out=True):
+        """demi_fuzz_generate: n_tests tests of Fuzzer(num_events, weights, send_gen, prefix, postfix), test i under
+        java.util.Random(seed_base + i) or seeds[i]; they stay resident for random_explore_tests(None, ..).  Returns
+        (events [n_tests, stride], n_ev [n_tests], n_batches [n_tests]); copy_out=False leaves the events on the device (None)."""
+        import numpy as np
+        par, keep = self.fuzz_params(num_events, weights, send_gen, prefix, postfix)
+        stride = int(lib().demi_fuzz_stride(C.byref(par)))
+        ev = np.zeros((n_tests, stride), dtype=T.EXT_EVENT_DTYPE) if copy_out and stride <= T.MAX_EXT_EVENTS else None     # (a longer stride is refused by the call)
+        n_ev = np.zeros(n_tests, dtype=np.uint32)
+        n_b = np.zeros(n_tests, dtype=np.uint32)
+        sp = None
+        if seeds is not None:
+            seeds = np.ascontiguousarray(seeds, dtype=np.uint64)
+            assert len(seeds) == n_tests
+            sp = seeds.ctypes.data
+        self._check(lib().demi_fuzz_generate(self._h, C.byref(par), C.c_uint64(seed_base), sp, n_tests,
+                                             ev.ctypes.data if ev is not None and n_tests else None, n_ev.ctypes.data, n_b.ctypes.data))
+        del keep
+        return ev, n_ev, n_b
+
+    def random_explore_tests(self, tests, executions, limits, seed_base=0, n_ev=None, n_tests=None):
+        """K1 with a workgroup per test: (verdicts [n_tests, executions], flags [n_tests]).  tests: [n_tests, stride] events with
+        their lengths n_ev (a list of event arrays is packed), or None for the first n_tests tests fuzz_generate left resident."""
+        import numpy as np
+        if tests is None:
+            assert n_tests is not None
+            tp, np_, stride = None, None, 0
+        else:
+            if not isinstance(tests, np.ndarray):
+                lens = [len(t) for t in tests]
+                packed = np.zeros((len(tests), max(lens + [1])), dtype=T.EXT_EVENT_DTYPE)
+                for i, t in enumerate(tests):
+                    packed[i, :lens[i]] = np.asarray(t, dtype=T.EXT_EVENT_DTYPE)
+                tests, n_ev = packed, lens
+            if n_ev is None:
+                raise ValueError("random_explore_tests: an array of tests needs n_ev, the length of every test")
+            tests = np.ascontiguousarray(tests, dtype=T.EXT_EVENT_DTYPE)
+            n_ev = np.ascontiguousarray(n_ev, dtype=np.uint32)
+            if tests.ndim != 2 or n_ev.shape != (tests.shape[0],):
+                raise ValueError("random_explore_tests: tests is [n_tests, stride] and n_ev [n_tests]")
+            n_tests, stride = tests.shape
+            tp, np_ = tests.ctypes.data, n_ev.ctypes.data
+        v = np.zeros((n_tests, executions), dtype=T.VERDICT_DTYPE)
+        f = np.zeros(n_tests, dtype=np.uint32)
+        self._check(lib().demi_random_explore_tests(self._h, C.c_uint64(seed_base), tp, np_, stride, n_tests, executions, C.byref(limits),
+                                                    v.ctypes.data, f.ctypes.data))
+        return v, f
+
+    def fuzz_campaign(self, num_events, weights, send_gen, prefix, limits, postfix=(), executions_per_test=1, tests_per_launch=256,
+                      max_tests=1024, test_seed_base=0, exec_seed_base=0):
+        """demi_fuzz_campaign: (result struct, the violating test's events or None)."""
+        import numpy as np
+        par, keep = self.fuzz_params(num_events, weights, send_gen, prefix, postfix)
+        cp = T.FuzzCampaignParams(test_seed_base=test_seed_base, exec_seed_base=exec_seed_base, executions_per_test=executions_per_test,
+                                  tests_per_launch=tests_per_launch, max_tests=max_tests)
+        res = T.FuzzCampaignResult()
+        cap = T.MAX_EXT_EVENTS
+        ev = np.zeros(cap, dtype=T.EXT_EVENT_DTYPE)
+        self._check(lib().demi_fuzz_campaign(self._h, C.byref(par), C.byref(cp), C.byref(limits), ev.ctypes.data, cap, C.byref(res)))
+        del keep
+        return res, (ev[:res.n_events].copy() if res.found else None)
 
     def random_ddmin(self, limits, params=None, seed_base=0, conjoined=None, cap=4096):
         """RunnerUtils.randomDDMin on the loaded trace, natively (demi_random_ddmin): (mcs indices, [(candidate indices, passes)]

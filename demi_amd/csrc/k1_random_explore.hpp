@@ -64,9 +64,23 @@ struct K1MultiArgs : K1Args {
 struct K1SpreadArgs : K1Args {
   uint32_t lanes_per_wave;      // 1 .. 64
 };
-template <bool MULTI, bool SPREAD = false> struct K1ArgsOf { typedef K1Args type; };
-template <> struct K1ArgsOf<true, false> { typedef K1MultiArgs type; };
-template <> struct K1ArgsOf<false, true> { typedef K1SpreadArgs type; };
+// TESTS variant (demi_random_explore_tests, the fuzz campaign): workgroup = one TEST of an array of external traces, e.g. the ones
+// k_fuzz_generate left on the device.  MULTI compacts a mask of the one loaded trace at that point; this front end copies the
+// workgroup's own trace into LDS instead, and from there the variant runs as MULTI does.  `n_ev` and `n_batches` of K1Args are
+// the launch's largest (they size the LDS), `trace` is unused.  Its own struct and template parameter, for SPREAD's reason.
+struct K1TestsArgs : K1Args {
+  const uint64_t* tests;        // [n_tests][stride] demi_ext_event as 8-byte words
+  const uint32_t* test_n_ev;    // [n_tests] a test's length, <= n_ev <= stride
+  uint32_t stride, n_tests;
+  uint32_t epc;                 // executions per test: execution k of every test uses seed_base + k (or seeds[k])
+  uint32_t populate_all;        // 1 = `exists` as given; 0 = the actors the TEST Start()s (what trace_load derives)
+  uint32_t* test_flags;         // [n_tests], zeroed by the host: bit 0 = some execution violated, bit 1 = some execution aborted on a capacity
+  uint32_t lanes_per_wave;      // 0 = 64; as in K1MultiArgs
+};
+template <bool MULTI, bool SPREAD = false, bool TESTS = false> struct K1ArgsOf { typedef K1Args type; };
+template <> struct K1ArgsOf<true, false, false> { typedef K1MultiArgs type; };
+template <> struct K1ArgsOf<false, true, false> { typedef K1SpreadArgs type; };
+template <> struct K1ArgsOf<false, false, true> { typedef K1TestsArgs type; };
 
 enum : int { PH_IDLE = 0, PH_INJECT = 1, PH_DISPATCH = 2, PH_FINISH = 3 };
 
@@ -190,17 +204,41 @@ __host__ __device__ inline size_t k1_lds_bytes(uint32_t code_len, uint32_t n_ev,
 // the candidate's mask in LDS before it builds the batch table, lane k runs execution k - no refill, a lane has one execution -
 // and a violating execution sets the candidate's flag.  Verdict cand * epc + k is what the plain kernel returns for
 // trace_load(candidate's events) and seed_base + k.
-template <bool REC, bool FIFO = false, bool CARRY = false, bool REBIN = false, bool MULTI = false, bool SPREAD = false>
-__global__ K1_LAUNCH_BOUNDS void k1_random_explore(const typename K1ArgsOf<MULTI, SPREAD>::type args) {
+// TESTS (demi_random_explore_tests): MULTI's shape over an ARRAY of traces - workgroup group i copies test i into LDS, lane k runs
+// its execution k, a violating execution sets the test's flag.  Verdict i * epc + k is what the plain kernel returns for
+// trace_load(test i) and seed_base + k.
+template <bool REC, bool FIFO = false, bool CARRY = false, bool REBIN = false, bool MULTI = false, bool SPREAD = false, bool TESTS = false>
+__global__ K1_LAUNCH_BOUNDS void k1_random_explore(const typename K1ArgsOf<MULTI, SPREAD, TESTS>::type args) {
+  static_assert(!TESTS || (!REC && !CARRY && !REBIN && !MULTI && !SPREAD), "a batch of tests runs the non-recording, per-execution-seed kernel");
   static_assert(!SPREAD || (!REC && !CARRY && !REBIN && !MULTI), "the spread variant is the plain per-execution kernel");
   static_assert(!REBIN || (!REC && !FIFO), "the re-binned kernel exists for the non-recording FullyRandom variant");
   static_assert(!MULTI || (!REC && !CARRY && !REBIN), "a frontier of candidates runs the non-recording, per-execution-seed kernel");
   static_assert(!BIG_TU || !REBIN, "the re-binned kernel packs an 8 x 8 reach row: tables of up to 8 actors");
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   Tables t;
-  unsigned char* extra = tables_load(t, smem, args.model, args.trace, args.n_ev, args.exists);
-  // MULTI: which candidate this workgroup evaluates, and which of its executions this lane runs
+  // MULTI / TESTS: which candidate (test) this workgroup evaluates, and which of its executions this lane runs
   uint32_t m_cand = 0, m_exec = 0;
+  const uint64_t* g_trace = args.trace;
+  if constexpr (TESTS) {
+    const uint32_t m_lpw = args.lanes_per_wave ? args.lanes_per_wave : 64u;
+    const uint32_t m_eff = (blockDim.x >> 6) * m_lpw;                    // executions per workgroup
+    const uint32_t m_wgpc = (args.epc + m_eff - 1) / m_eff;
+    m_cand = blockIdx.x / m_wgpc;                                        // (< n_tests: the grid is n_tests * m_wgpc workgroups)
+    m_exec = (threadIdx.x & 63u) < m_lpw ? (blockIdx.x % m_wgpc) * m_eff + (threadIdx.x >> 6) * m_lpw + (threadIdx.x & 63u) : 0xFFFFFFFFu;
+    g_trace = args.tests + (size_t)m_cand * args.stride;                 // (n_ev <= stride words of the row are copied; the test's own come first)
+  }
+  unsigned char* extra = tables_load(t, smem, args.model, g_trace, args.n_ev, args.exists);
+  if constexpr (TESTS) {
+    t.E = args.test_n_ev[m_cand];
+    if (!args.populate_all) {                 // populateActorSystem creates the actors the trace Start()s (ExternalEventInjector.scala:371-378)
+      uint32_t ex = 0;
+      for (uint32_t i = 0; i < t.E; i++) {
+        const uint64_t ev = t.trace[i];
+        if (((uint32_t)ev & 0xFF) == DEMI_EV_START) ex |= 1u << ((uint32_t)(ev >> 8) & 0xFF);
+      }
+      t.exists = ex;
+    }
+  }
   if constexpr (MULTI) {
     // (lanes_per_wave < 64: a candidate's executions on the first lanes of more waves - SPREAD above; 64: lane k = execution k)
     const uint32_t m_lpw = args.lanes_per_wave ? args.lanes_per_wave : 64u;
@@ -662,6 +700,10 @@ __global__ K1_LAUNCH_BOUNDS void k1_random_explore(const typename K1ArgsOf<MULTI
           const uint32_t cf = ((v.x & DEMI_V_VIOLATION) ? 1u : 0u) | ((v.x & DEMI_OVF_ANY) ? 2u : 0u);
           if (cf) atomicOr(&args.cand_flags[m_cand], cf);
         }
+        if constexpr (TESTS) {
+          const uint32_t cf = ((v.x & DEMI_V_VIOLATION) ? 1u : 0u) | ((v.x & DEMI_OVF_ANY) ? 2u : 0u);
+          if (cf) atomicOr(&args.test_flags[m_cand], cf);
+        }
         // reset the simulator for the next schedule
         ph = PH_IDLE;
         if (CARRY && !(v.x & DEMI_V_VIOLATION) && sched + 1 < inst_end) {
@@ -680,6 +722,12 @@ __global__ K1_LAUNCH_BOUNDS void k1_random_explore(const typename K1ArgsOf<MULTI
         if (!exhausted) {
           exhausted = true;
           if (m_exec < args.epc && m_cand < args.n_cand) { ph = PH_INJECT; fresh = true; sched = (uint64_t)m_cand * args.epc + m_exec; }
+        }
+        if (__ballot(ph != PH_IDLE) == 0) break;
+      } else if constexpr (TESTS) {
+        if (!exhausted) {
+          exhausted = true;
+          if (m_exec < args.epc && m_cand < args.n_tests) { ph = PH_INJECT; fresh = true; sched = (uint64_t)m_cand * args.epc + m_exec; }
         }
         if (__ballot(ph != PH_IDLE) == 0) break;
       } else {
@@ -724,7 +772,7 @@ __global__ K1_LAUNCH_BOUNDS void k1_random_explore(const typename K1ArgsOf<MULTI
           // new execution: `new FullyRandom(seed)`; populateActorSystem isolates every created actor
           // (ExternalEventInjector.scala:371-378)
           if (!CARRY || exec_no == 0) {
-            const uint64_t unit = MULTI ? (uint64_t)m_exec : CARRY ? inst : sched;
+            const uint64_t unit = (MULTI || TESTS) ? (uint64_t)m_exec : CARRY ? inst : sched;
             const uint64_t seed = args.seeds ? args.seeds[unit] : args.seed_base + unit;
             rng = jr_seed(seed);
             te_rng = rng;                // SrcDstFIFO: both generators are `new Random(seed)`

@@ -207,3 +207,117 @@ def raft_trace(n_actors: int, n_events: int, seed: int, weights: FuzzerWeights =
             if len(tr) == n_events:
                 return tr
     raise ValueError("cannot build a trace of exactly %d events" % n_events)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# A message generator that can cross the C ABI (include/demi_gpu.h demi_fuzz_send_gen).  Fuzzer takes the application's
+# MessageGenerator closure (Fuzzer.scala:31-35); k_fuzz_generate (csrc/k_fuzz.hpp) cannot call one, so the usual closures
+# are restated as data: 1..8 alternatives (msg_type, target, p0, p1).  The draw order is the contract between this mirror
+# and the kernel: the alternative with next_int(n) only when n > 1, then the target, then p0, then p1.
+FUZZ_MAX_ALTS = 8
+TARGET_RANDOM_ALIVE, TARGET_FIXED = 0, 1
+FIELD_CONST, FIELD_COUNTER, FIELD_RANDOM = 0, 1, 2
+
+RANDOM_ALIVE = (TARGET_RANDOM_ALIVE, 0)
+COUNTER = (FIELD_COUNTER, 0)
+
+
+def FIXED(actor):
+    return (TARGET_FIXED, int(actor))
+
+
+def CONST(v):
+    return (FIELD_CONST, int(v))
+
+
+def RANDOM(bound):
+    return (FIELD_RANDOM, int(bound))
+
+
+SEND_ALT_DTYPE = np.dtype([("msg_type", "u1"), ("target_kind", "u1"), ("target_actor", "u1"), ("p0_kind", "u1"),
+                           ("p1_kind", "u1"), ("pad", "u1", (3,)), ("p0_arg", "<u4"), ("p1_arg", "<u4")])     # demi_fuzz_send_alt
+SEND_GEN_DTYPE = np.dtype([("n_alts", "<u4"), ("field_bits", "<u4"), ("alts", SEND_ALT_DTYPE, (FUZZ_MAX_ALTS,))])  # demi_fuzz_send_gen
+
+
+class SendGenerator:
+    """alternatives: [(msg_type, target, p0, p1)] with target RANDOM_ALIVE / FIXED(actor) and p0, p1 each CONST(v) /
+    COUNTER / RANDOM(bound).  COUNTER = the Sends generated so far in this test, starting at 1, masked to the field's
+    width (field_bits: 8, or 16 for a DEMI_MODEL_WIDE table).  Callable as generate_fuzz_test's message_gen; the counter
+    restarts whenever it is handed a generator it has not seen, i.e. with every generate_fuzz_test."""
+
+    def __init__(self, alternatives, field_bits: int = 8):
+        alternatives = [tuple(a) for a in alternatives]
+        if not 1 <= len(alternatives) <= FUZZ_MAX_ALTS:
+            raise ValueError("a SendGenerator holds 1..%d alternatives" % FUZZ_MAX_ALTS)
+        if field_bits not in (8, 16):
+            raise ValueError("field_bits is 8, or 16 for a wide table")
+        lim = 1 << field_bits
+        for msg_type, target, p0, p1 in alternatives:
+            if not 0 <= msg_type < 32:
+                raise ValueError("message type %r" % (msg_type,))
+            if target[0] not in (TARGET_RANDOM_ALIVE, TARGET_FIXED) or not 0 <= target[1] < 16:
+                raise ValueError("target %r" % (target,))
+            for kind, arg in (p0, p1):
+                if kind == FIELD_CONST and not 0 <= arg < lim:
+                    raise ValueError("CONST(%d) does not fit %d bits" % (arg, field_bits))
+                if kind == FIELD_RANDOM and not 1 <= arg <= min(lim, 256):
+                    raise ValueError("RANDOM(%d): the bound is 1..%d" % (arg, min(lim, 256)))
+                if kind not in (FIELD_CONST, FIELD_COUNTER, FIELD_RANDOM):
+                    raise ValueError("payload field %r" % ((kind, arg),))
+        self.alternatives, self.field_bits = alternatives, field_bits
+        self._rng, self.counter = None, 0
+
+    def __call__(self, rng, alive):
+        if rng is not self._rng:
+            self._rng, self.counter = rng, 0
+        self.counter += 1
+        alts = self.alternatives
+        msg_type, target, p0, p1 = alts[rng.next_int(len(alts))] if len(alts) > 1 else alts[0]
+        if target[0] == TARGET_RANDOM_ALIVE:
+            a = alive.get_random() if len(alive) else 0
+        else:
+            a = target[1]
+        mask = (1 << self.field_bits) - 1
+
+        def field(f):
+            if f[0] == FIELD_CONST:
+                return f[1]
+            if f[0] == FIELD_COUNTER:
+                return self.counter & mask
+            return rng.next_int(f[1])
+
+        v0 = field(p0)
+        v1 = field(p1)
+        return send(a, msg_type, v0, v1)
+
+    def to_struct(self) -> np.ndarray:
+        s = np.zeros(1, dtype=SEND_GEN_DTYPE)
+        s["n_alts"], s["field_bits"] = len(self.alternatives), self.field_bits
+        for i, (msg_type, target, p0, p1) in enumerate(self.alternatives):
+            a = s["alts"][0][i]
+            a["msg_type"], a["target_kind"], a["target_actor"] = msg_type, target[0], target[1]
+            a["p0_kind"], a["p0_arg"], a["p1_kind"], a["p1_arg"] = p0[0], p0[1], p1[0], p1[1]
+        return s
+
+
+def raft_send_generator() -> SendGenerator:
+    """raft_trace's closure as a descriptor: ClientRequest(counter) to a random live node."""
+    from .model import M_CLIENT
+    return SendGenerator([(M_CLIENT, RANDOM_ALIVE, COUNTER, CONST(0))])
+
+
+def fuzz_stride(num_events: int, prefix, postfix=()) -> int:
+    """The longest test generate_fuzz_test(num_events, ..) can return: prefix + num_events + postfix + the final WaitQuiescence."""
+    return len(prefix) + num_events + len(postfix) + 1
+
+
+def fuzz_thresholds(weights: FuzzerWeights):
+    """(totalMass, cumulative kill, send, partition, unpartition), each computed by the very expressions of
+    generate_fuzz_test: the doubles the device multiplies by and compares against."""
+    weights_list = [weights.kill, weights.send, weights.partition, weights.unpartition]
+    total = sum(weights_list) + weights.wait_quiescence
+    cur, cum = 0.0, []
+    for w in weights_list:
+        cur += w
+        cum.append(cur)
+    return (total, *cum)

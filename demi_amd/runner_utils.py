@@ -78,6 +78,99 @@ def fuzz(generateFuzzTest: Callable[[int], np.ndarray], schedulerConfig: Schedul
     return None
 
 
+def fuzz_campaign(fuzzer_args, schedulerConfig: SchedulerConfig,
+                  validate_replay: Optional[Callable[[], ReplayScheduler]] = None, invariant_check_interval: int = 30,
+                  maxMessages: Optional[int] = None, randomizationStrategyCtor: Callable[[], object] = FullyRandom,
+                  computeProvenance: bool = True, violationWereLookingFor: Callable[[ViolationFingerprint], bool] = lambda f: True,
+                  executions_per_test: int = 64, max_tests: int = 1024, tests_per_launch: int = 256, test_seed_base: int = 0,
+                  provenance_device: Optional[int] = 0, device: int = 0, p_max: int = 64, specialize: bool = False
+                  ) -> Optional[Tuple[EventTrace, ViolationFingerprint, np.ndarray, np.ndarray]]:
+    """fuzz() with the test axis on the device: what fuzz(lambda i: generate_fuzz_test(.., seed = test_seed_base + i), ..) returns
+    for the same executions_per_test and max_tests - (trace, violation, initialTrace, filtered) or None - found by launches of
+    tests_per_launch generated tests each (demi_fuzz_campaign: k_fuzz_generate, K1 with a workgroup per test, the per-test flags).
+
+    fuzzer_args: (num_events, weights, send_generator, prefix[, postfix]) - Fuzzer's constructor arguments with the
+    MessageGenerator as a fuzzer.SendGenerator.  The one (test, execution) the device reports is re-run through the recording
+    path (RandomScheduler.explore's own last step) for its EventTrace; replay validation, violationWereLookingFor and the
+    provenance pruning are fuzz()'s, and a test they reject sends the campaign on from the test after it.  When an execution
+    before the reported one was aborted on a capacity, the campaign goes on with the largest pending set (fuzz() decides such an
+    execution alone with it; verdicts without an overflow do not depend on p_max); CapacityExceeded if that does not suffice."""
+    from . import _native
+    from .schedulers import CapacityExceeded, SrcDstFIFO
+    num_events, weights, send_gen, prefix = fuzzer_args[:4]
+    postfix = fuzzer_args[4] if len(fuzzer_args) > 4 else ()
+    model = schedulerConfig.model
+    if model is None or model.inv_kind == T.INV_NONE:
+        raise ValueError("Must invoke setInvariant before test()")
+    strategy = randomizationStrategyCtor()
+    exec_seed_base = strategy.seed
+    mm = 0 if maxMessages is None or maxMessages >= 0x7FFFFFFF else maxMessages
+    lim = T.Limits(mm, max(0, invariant_check_interval), p_max, 0, 0, 1 if schedulerConfig.populate_all_actors else 0,
+                   T.STRATEGY_SRC_DST_FIFO if isinstance(strategy, SrcDstFIFO) else T.STRATEGY_FULLY_RANDOM)
+    ctx = _native.Context(device)
+    try:
+        ctx.model_load(model.to_struct())
+        if getattr(model, "compiled_only", False) or specialize:
+            ctx.model_specialize()
+        start = 0
+        while start < max_tests:
+            res, fuzzTest = ctx.fuzz_campaign(num_events, weights, send_gen, prefix, lim, postfix=postfix,
+                                              executions_per_test=executions_per_test, tests_per_launch=tests_per_launch,
+                                              max_tests=max_tests - start, test_seed_base=test_seed_base + start,
+                                              exec_seed_base=exec_seed_base)
+            if res.capacity_aborts:
+                # an execution aborted on a capacity has no verdict.  fuzz() decides it alone with the largest pending set; a verdict
+                # does not depend on p_max unless the execution overflows, so the campaign from this test on with the largest
+                # pending set answers what fuzz() answers.  Aborts that remain are beyond the engine, as they are for fuzz().
+                if lim.p_max >= T.MAX_PENDING:
+                    raise CapacityExceeded("%d tests of the campaign have executions beyond p_max = %d" % (res.capacity_aborts, lim.p_max))
+                lim.p_max = T.MAX_PENDING
+                continue
+            if not res.found:
+                return None
+            start += int(res.test_index) + 1
+            ctx.trace_load(fuzzTest)
+            v, rec = ctx.random_get_trace(exec_seed_base + int(res.exec_index), lim)
+            assert v.flags & T.V_VIOLATION and int(v.fingerprint) == int(res.verdict.fingerprint)
+            trace = EventTrace(rec, fuzzTest[:T.verdict_trace_idx(v.flags)])
+            violation = ViolationFingerprint(int(v.fingerprint), model.fp_match_mask)
+            if not violationWereLookingFor(violation):
+                continue
+            if validate_replay is not None:
+                replayer = validate_replay()
+                deterministic = True
+                try:
+                    rv = replayer.replay(trace, violation)
+                    if not (int(rv["flags"]) & T.V_VIOLATION):
+                        deterministic = False
+                except ReplayException:
+                    deterministic = False
+                finally:
+                    replayer.shutdown()
+                if not deterministic:
+                    continue
+            initialTrace = dpor_initial_trace(trace, model)
+            if not computeProvenance:
+                filtered = initialTrace[:0]
+            elif provenance_device is not None:
+                filtered = _prune_on(provenance_device, initialTrace, violation)       # (a context of its own, as in fuzz())
+            else:
+                filtered = pruneConcurrentEvents(initialTrace, violation.affectedNodes())
+            return trace, violation, initialTrace, filtered
+        return None
+    finally:
+        ctx.close()
+
+
+def _prune_on(device, initialTrace, violation):
+    from . import _native
+    pctx = _native.Context(device)
+    try:
+        return pruneConcurrentEvents(initialTrace, violation.affectedNodes(), ctx=pctx)
+    finally:
+        pctx.close()
+
+
 def wildcardDDMin(schedulerConfig: SchedulerConfig, originalTrace: EventTrace, violation: ViolationFingerprint,
                   resolutionStrategy=None, stats: Optional[MinimizationStats] = None, native: bool = False, speculative_depth: int = 0,
                   max_candidates: int = 0, sequential: bool = False, oracle=None, device: int = 0, p_max: int = 64):

@@ -164,6 +164,37 @@ class DdminParams(C.Structure):
         super().__init__(depth, max_candidates, check_unmodified, verify_mcs)
 
 
+class FuzzSendAlt(C.Structure):
+    """demi_fuzz_send_alt"""
+    _fields_ = [("msg_type", C.c_uint8), ("target_kind", C.c_uint8), ("target_actor", C.c_uint8), ("p0_kind", C.c_uint8),
+                ("p1_kind", C.c_uint8), ("pad", C.c_uint8 * 3), ("p0_arg", C.c_uint32), ("p1_arg", C.c_uint32)]
+
+
+class FuzzSendGen(C.Structure):
+    """demi_fuzz_send_gen"""
+    _fields_ = [("n_alts", C.c_uint32), ("field_bits", C.c_uint32), ("alts", FuzzSendAlt * 8)]
+
+
+class FuzzParams(C.Structure):
+    """demi_fuzz_params"""
+    _fields_ = [("num_events", C.c_uint32), ("n_prefix", C.c_uint32), ("n_postfix", C.c_uint32), ("pad", C.c_uint32),
+                ("prefix", C.c_void_p), ("postfix", C.c_void_p), ("total_mass", C.c_double), ("cum", C.c_double * 4),
+                ("gen", FuzzSendGen)]
+
+
+class FuzzCampaignParams(C.Structure):
+    """demi_fuzz_campaign_params"""
+    _fields_ = [("test_seed_base", C.c_uint64), ("exec_seed_base", C.c_uint64), ("executions_per_test", C.c_uint32),
+                ("tests_per_launch", C.c_uint32), ("max_tests", C.c_uint32), ("pad", C.c_uint32)]
+
+
+class FuzzCampaignResult(C.Structure):
+    """demi_fuzz_campaign_result"""
+    _fields_ = [("found", C.c_uint32), ("test_index", C.c_uint32), ("exec_index", C.c_uint32), ("n_events", C.c_uint32),
+                ("tests_run", C.c_uint32), ("launches", C.c_uint32), ("capacity_aborts", C.c_uint32), ("pad", C.c_uint32),
+                ("verdict", Verdict)]
+
+
 class RandomDdminParams(C.Structure):
     """demi_random_ddmin_params"""
     _fields_ = [("executions", C.c_uint32), ("depth", C.c_uint32), ("max_candidates", C.c_uint32), ("check_unmodified", C.c_uint32),

@@ -943,6 +943,103 @@ int demi_random_explore_sharded(demi_ctx* ctx, uint64_t seed_base, uint64_t n_to
 int demi_replay_batch_sharded(demi_ctx* ctx, const uint64_t* masks /* [n][4] */, uint64_t n, const demi_limits* limits,
                               demi_verdict* out);
 
+/* ---------------------------------------------------------- fuzz campaigns: a batch of generated tests per launch
+ * RunnerUtils.fuzz (RunnerUtils.scala:62-147) draws a fresh test with Fuzzer.generateFuzzTest (Fuzzer.scala:84-175) and runs
+ * random executions of it, over and over.  Here the tests of a launch are generated ON the device (one test per lane), explored
+ * by K1 with a workgroup per test, and reduced to "the first test that violates".
+ *
+ * Fuzzer takes the application's MessageGenerator closure; a closure cannot cross this boundary, so the generator is described:
+ * 1..DEMI_FUZZ_MAX_ALTS alternatives, each (msg_type, target, p0, p1).
+ *   target: DEMI_FUZZ_TARGET_RANDOM_ALIVE = alive.getRandomElement, or actor 0 WITHOUT a draw when nobody is alive;
+ *           DEMI_FUZZ_TARGET_FIXED = target_actor.
+ *   p0, p1: DEMI_FUZZ_FIELD_CONST = arg; DEMI_FUZZ_FIELD_COUNTER = the number of Sends generated so far in this test (this one
+ *           included: the first Send sees 1), masked to field_bits; DEMI_FUZZ_FIELD_RANDOM = nextInt(arg), 1 <= arg <= 256.
+ * THE DRAW ORDER of one generated Send, which the host mirror (demi_amd/fuzzer.py SendGenerator) and k_fuzz_generate share:
+ *   1. the alternative: nextInt(n_alts) - only when n_alts > 1;   2. the target (RANDOM_ALIVE with somebody alive: nextInt(|alive|));
+ *   3. p0 (RANDOM: nextInt(p0_arg));   4. p1 (RANDOM: nextInt(p1_arg)).
+ * The draws of generateFuzzTest around it: per event one nextDouble() = ((next(26) << 27) + next(27)) * 2^-53, scaled by
+ * total_mass and walked through the cumulative thresholds in the order kill, send, partition, unpartition (else WaitQuiescence);
+ * Kill: nextInt(|alive|) with swap-remove (nobody alive: the test ENDS there, without postfix and final WaitQuiescence);
+ * Partition / UnPartition: nextInt(|set|) with swap-remove from one RandomizedHashSet and append to the other (empty set: a new
+ * double is drawn); a WaitQuiescence right after a WaitQuiescence is drawn again. */
+#define DEMI_FUZZ_MAX_ALTS 8
+/* The redraws must end on the device: the event classes that always yield an event - Send, Kill (with nobody alive it ends the test)
+ * and, with two or more nodes, Partition and UnPartition together (min of the two weights) - must hold at least this share of
+ * total_mass whenever num_events > 0.  Weights below it (e.g. WaitQuiescence alone: the second one would be redrawn forever) are refused. */
+#define DEMI_FUZZ_MIN_PROGRESS (1.0 / 65536.0)
+typedef enum { DEMI_FUZZ_TARGET_RANDOM_ALIVE = 0, DEMI_FUZZ_TARGET_FIXED = 1 } demi_fuzz_target;
+typedef enum { DEMI_FUZZ_FIELD_CONST = 0, DEMI_FUZZ_FIELD_COUNTER = 1, DEMI_FUZZ_FIELD_RANDOM = 2 } demi_fuzz_field;
+typedef struct {
+  uint8_t msg_type;
+  uint8_t target_kind;     /* demi_fuzz_target */
+  uint8_t target_actor;    /* DEMI_FUZZ_TARGET_FIXED */
+  uint8_t p0_kind, p1_kind; /* demi_fuzz_field */
+  uint8_t pad[3];
+  uint32_t p0_arg, p1_arg; /* CONST: the value; RANDOM: the bound */
+} demi_fuzz_send_alt;      /* 16 bytes */
+typedef struct {
+  uint32_t n_alts;         /* 1..DEMI_FUZZ_MAX_ALTS */
+  uint32_t field_bits;     /* width COUNTER is masked to and CONST / RANDOM must fit: 8, or 16 for a DEMI_MODEL_WIDE table */
+  demi_fuzz_send_alt alts[DEMI_FUZZ_MAX_ALTS];
+} demi_fuzz_send_gen;      /* 136 bytes */
+typedef struct {
+  uint32_t num_events;     /* Fuzzer's num_events: generated events between prefix and postfix */
+  uint32_t n_prefix, n_postfix;
+  uint32_t pad;
+  const demi_ext_event* prefix;    /* must Start() at least one actor; the Start()ed actors are the fuzzer's nodes */
+  const demi_ext_event* postfix;   /* may be NULL when n_postfix == 0 */
+  /* FuzzerWeights as the doubles the device uses, summed by the caller in FuzzerWeights' own order (Fuzzer.scala:24-57):
+   * cum[0] = kill, cum[1] = cum[0] + send, cum[2] = cum[1] + partition, cum[3] = cum[2] + unpartition,
+   * total_mass = that sum + wait_quiescence.  The device multiplies one nextDouble by total_mass and compares. */
+  double total_mass;
+  double cum[4];
+  demi_fuzz_send_gen gen;
+} demi_fuzz_params;
+/* The largest length a generated test can have: n_prefix + num_events + n_postfix + 1.  Every test occupies that many
+ * demi_ext_event in the arrays below (the events behind a test's length are zero). */
+uint32_t demi_fuzz_stride(const demi_fuzz_params* params);
+/* Generates n_tests tests for the loaded model: test i under java.util.Random(seed_base + i), or seeds[i].  They stay resident in
+ * the context for demi_random_explore_tests(tests = NULL); each out_* may be NULL: out_events [n_tests][stride], out_n_ev
+ * [n_tests] (a test's length), out_n_batches [n_tests] (its injection batches: WaitQuiescence events + 1).
+ * DEMI_ERR_INVALID_ARG, with the limit in demi_last_error: a stride above DEMI_MAX_EXT_EVENTS, a prefix without a Start, weights
+ * that are all zero (total_mass <= 0) or cannot guarantee progress (DEMI_FUZZ_MIN_PROGRESS), an event or a generator alternative
+ * the loaded model cannot take. */
+int demi_fuzz_generate(demi_ctx* ctx, const demi_fuzz_params* params, uint64_t seed_base, const uint64_t* seeds, uint32_t n_tests,
+                       demi_ext_event* out_events, uint32_t* out_n_ev, uint32_t* out_n_batches);
+/* K1 with a workgroup per TEST: out_verdicts[i * executions + k] is, byte for byte, what demi_trace_load(test i) followed by
+ * demi_random_explore(seed_base + k) returns.  tests [n_tests][stride] with n_ev [n_tests] their lengths, or tests = NULL (n_ev,
+ * stride ignored) for the tests the last demi_fuzz_generate left in the context (n_tests <= what it generated).  out_flags
+ * [n_tests]: bit 0 = some execution of the test violated (limits.looking_for applies), bit 1 = some execution was aborted on a
+ * capacity.  Either output may be NULL.  The loaded trace, if any, is neither used nor changed.  DEMI_ERR_INVALID_ARG for a
+ * DEMI_MODEL_PAYLOADS table (a generated Send has two fields; per-test payload areas are not built). */
+int demi_random_explore_tests(demi_ctx* ctx, uint64_t seed_base, const demi_ext_event* tests, const uint32_t* n_ev, uint32_t stride,
+                              uint32_t n_tests, uint32_t executions, const demi_limits* limits, demi_verdict* out_verdicts,
+                              uint32_t* out_flags);
+/* The campaign: launches of tests_per_launch tests (generate, explore, reduce) until the launch that holds the first violating
+ * test, or max_tests tests.  Test t runs under test_seed_base + t, its execution k under exec_seed_base + k. */
+typedef struct {
+  uint64_t test_seed_base, exec_seed_base;
+  uint32_t executions_per_test;
+  uint32_t tests_per_launch;   /* 0 = 256 */
+  uint32_t max_tests;
+  uint32_t pad;
+} demi_fuzz_campaign_params;
+typedef struct {
+  uint32_t found;              /* 1: a test violated */
+  uint32_t test_index;         /* the lowest violating test index */
+  uint32_t exec_index;         /* that test's lowest violating execution index */
+  uint32_t n_events;           /* its length (events copied to out_events) */
+  uint32_t tests_run, launches;
+  uint32_t capacity_aborts;    /* tests BEFORE the reported one (all tests, when none violates) with an execution aborted on a capacity,
+                                  plus 1 when the reported test has an aborted execution before exec_index: such executions have no
+                                  verdict, so with capacity_aborts != 0 "the first violation" holds only for limits.p_max raised */
+  uint32_t pad;
+  demi_verdict verdict;        /* of (test_index, exec_index) */
+} demi_fuzz_campaign_result;
+int demi_fuzz_campaign(demi_ctx* ctx, const demi_fuzz_params* params, const demi_fuzz_campaign_params* campaign,
+                       const demi_limits* limits, demi_ext_event* out_events /* [cap] */, uint32_t cap,
+                       demi_fuzz_campaign_result* result);
+
 /* ---------------------------------------------------------- measurement helpers (no reference counterpart)
  * Used by bench.py and the profiling scripts so that the figures beside the throughput are measured on the box that
  * prints them: the shader clock under load (s_memtime cycles per 100 MHz wall_clock64 tick) and the cycles one SIMD spends

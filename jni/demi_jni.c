@@ -728,3 +728,117 @@ JNIEXPORT jint JNICALL FN(randomExploreSharded)(JNIEnv* e, jclass c, jlong h, jl
   SET_LONGS(count, 1, &cn);
   return rc;
 }
+
+/* ---- fuzz campaigns (demi_fuzz_generate / demi_random_explore_tests / demi_fuzz_campaign).  A Fuzzer crosses as: numEvents; prefix,
+ *      postfixOrNull: byte[8 * n] (demi_ext_event); weightBits: long[5] = Double.doubleToRawLongBits of total_mass, cum[0 .. 3] (summed by
+ *      the caller in FuzzerWeights' own order); gen: byte[136] (demi_fuzz_send_gen).  The arrays are copied: nothing of them is pinned
+ *      while the device works. */
+typedef struct { demi_fuzz_params par; demi_ext_event fix[2 * DEMI_MAX_EXT_EVENTS]; } jni_fuzzer;
+static int fuzzer_of(JNIEnv* e, jint numEvents, jbyteArray prefix, jbyteArray postfixOrNull, jlongArray weightBits, jbyteArray gen, jni_fuzzer* f) {
+  const int64_t np = LEN(prefix), nq = postfixOrNull ? LEN(postfixOrNull) : 0;
+  jlong w[5];
+  memset(f, 0, sizeof *f);
+  if (numEvents < 0 || np < 0 || np % 8 || nq % 8 || np / 8 > DEMI_MAX_EXT_EVENTS || nq / 8 > DEMI_MAX_EXT_EVENTS || LEN(weightBits) != 5 ||
+      LEN(gen) != (int64_t)sizeof(demi_fuzz_send_gen))
+    return DEMI_ERR_INVALID_ARG;
+  (*e)->GetByteArrayRegion(e, prefix, 0, (jsize)np, (jbyte*)f->fix);
+  if (nq) (*e)->GetByteArrayRegion(e, postfixOrNull, 0, (jsize)nq, (jbyte*)(f->fix + DEMI_MAX_EXT_EVENTS));
+  (*e)->GetByteArrayRegion(e, gen, 0, (jsize)sizeof(demi_fuzz_send_gen), (jbyte*)&f->par.gen);
+  {
+    void* wb = LONGS(weightBits);
+    if (LOST(weightBits, wb)) return DEMI_ERR_INVALID_ARG;
+    memcpy(w, wb, sizeof w);
+    PUT_LONGS(weightBits, wb, JNI_ABORT);
+  }
+  memcpy(&f->par.total_mass, &w[0], sizeof(double));
+  memcpy(f->par.cum, &w[1], 4 * sizeof(double));
+  f->par.num_events = (uint32_t)numEvents; f->par.n_prefix = (uint32_t)(np / 8); f->par.n_postfix = (uint32_t)(nq / 8);
+  f->par.prefix = f->fix; f->par.postfix = nq ? f->fix + DEMI_MAX_EXT_EVENTS : NULL;
+  return DEMI_OK;
+}
+
+/* eventsOrNull: byte[8 * nTests * stride] with stride = prefix + numEvents + postfix + 1 events; nEv: int[nTests]; nBatchesOrNull: int[nTests];
+ * seedsOrNull: long[nTests] */
+JNIEXPORT jint JNICALL FN(fuzzGenerate)(JNIEnv* e, jclass c, jlong h, jint numEvents, jbyteArray prefix, jbyteArray postfixOrNull,
+                                       jlongArray weightBits, jbyteArray gen, jlong seedBase, jlongArray seedsOrNull, jint nTests,
+                                       jbyteArray eventsOrNull, jintArray nEv, jintArray nBatchesOrNull) {
+  jni_fuzzer f;
+  (void)c;
+  if (fuzzer_of(e, numEvents, prefix, postfixOrNull, weightBits, gen, &f) || nTests < 0 || !nEv || LEN(nEv) < nTests ||
+      (nBatchesOrNull && LEN(nBatchesOrNull) < nTests) || (seedsOrNull && LEN(seedsOrNull) < nTests) ||
+      (eventsOrNull && LEN(eventsOrNull) < 8 * (int64_t)nTests * (int64_t)demi_fuzz_stride(&f.par)))
+    return DEMI_ERR_INVALID_ARG;
+  void* sd = LONGS(seedsOrNull);
+  void* ev = BYTES(eventsOrNull);
+  void* ne = INTS(nEv);
+  void* nb = INTS(nBatchesOrNull);
+  jint rc = (LOST(seedsOrNull, sd) || LOST(eventsOrNull, ev) || LOST(nEv, ne) || LOST(nBatchesOrNull, nb)) ? DEMI_ERR_INVALID_ARG
+            : demi_fuzz_generate(CTX(h), &f.par, (uint64_t)seedBase, (const uint64_t*)sd, (uint32_t)nTests, (demi_ext_event*)ev, (uint32_t*)ne,
+                                 (uint32_t*)nb);
+  PUT_INTS(nBatchesOrNull, nb, 0);
+  PUT_INTS(nEv, ne, 0);
+  PUT_BYTES(eventsOrNull, ev, 0);
+  PUT_LONGS(seedsOrNull, sd, JNI_ABORT);
+  return rc;
+}
+
+/* testsOrNull: byte[8 * nTests * stride] with nEvOrNull: int[nTests], or null for the tests fuzzGenerate left in the context;
+ * verdictsOrNull: long[2 * nTests * executions]; flags: int[nTests] (bit 0: some execution violates, bit 1: some execution aborted) */
+JNIEXPORT jint JNICALL FN(randomExploreTests)(JNIEnv* e, jclass c, jlong h, jlong seedBase, jbyteArray testsOrNull, jintArray nEvOrNull,
+                                             jint stride, jint nTests, jint executions, jintArray limits, jlongArray verdictsOrNull,
+                                             jintArray flags) {
+  demi_limits lim;
+  (void)c;
+  if (limits_of(e, limits, &lim) || nTests < 0 || executions < 0 || stride < 0 || !flags || LEN(flags) < nTests ||
+      (verdictsOrNull && LEN(verdictsOrNull) < 2 * (int64_t)nTests * (int64_t)executions) ||
+      (testsOrNull && (!nEvOrNull || LEN(nEvOrNull) < nTests || LEN(testsOrNull) < 8 * (int64_t)nTests * (int64_t)stride)))
+    return DEMI_ERR_INVALID_ARG;
+  void* t = BYTES(testsOrNull);
+  void* ne = testsOrNull ? INTS(nEvOrNull) : NULL;
+  void* v = LONGS(verdictsOrNull);
+  void* fl = INTS(flags);
+  jint rc = (LOST(testsOrNull, t) || (testsOrNull && LOST(nEvOrNull, ne)) || LOST(verdictsOrNull, v) || LOST(flags, fl)) ? DEMI_ERR_INVALID_ARG
+            : demi_random_explore_tests(CTX(h), (uint64_t)seedBase, (const demi_ext_event*)t, (const uint32_t*)ne, (uint32_t)stride,
+                                        (uint32_t)nTests, (uint32_t)executions, &lim, (demi_verdict*)v, (uint32_t*)fl);
+  PUT_INTS(flags, fl, 0);
+  PUT_LONGS(verdictsOrNull, v, 0);
+  if (testsOrNull) PUT_INTS(nEvOrNull, ne, JNI_ABORT);
+  PUT_BYTES(testsOrNull, t, JNI_ABORT);
+  return rc;
+}
+
+/* campaign: long[5] = test_seed_base, exec_seed_base, executions_per_test, tests_per_launch, max_tests; events: byte[8 * 255] (the
+ * violating test); result: long[9] = found, test_index, exec_index, n_events, tests_run, launches, capacity_aborts, the verdict's
+ * flags | fingerprint << 32, its hash */
+JNIEXPORT jint JNICALL FN(fuzzCampaign)(JNIEnv* e, jclass c, jlong h, jint numEvents, jbyteArray prefix, jbyteArray postfixOrNull,
+                                       jlongArray weightBits, jbyteArray gen, jlongArray campaign, jintArray limits, jbyteArray events,
+                                       jlongArray result) {
+  jni_fuzzer f;
+  demi_limits lim;
+  demi_fuzz_campaign_params cp;
+  demi_fuzz_campaign_result res;
+  jlong o[9];
+  (void)c;
+  if (fuzzer_of(e, numEvents, prefix, postfixOrNull, weightBits, gen, &f) || limits_of(e, limits, &lim) || LEN(campaign) != 5 ||
+      LEN(result) != 9 || !events || LEN(events) < 8 * DEMI_MAX_EXT_EVENTS)
+    return DEMI_ERR_INVALID_ARG;
+  memset(&cp, 0, sizeof cp);
+  {
+    void* cb = LONGS(campaign);
+    if (LOST(campaign, cb)) return DEMI_ERR_INVALID_ARG;
+    const jlong* q = (const jlong*)cb;
+    cp.test_seed_base = (uint64_t)q[0]; cp.exec_seed_base = (uint64_t)q[1]; cp.executions_per_test = (uint32_t)q[2];
+    cp.tests_per_launch = (uint32_t)q[3]; cp.max_tests = (uint32_t)q[4];
+    PUT_LONGS(campaign, cb, JNI_ABORT);
+  }
+  void* ev = BYTES(events);
+  jint rc = LOST(events, ev) ? DEMI_ERR_INVALID_ARG
+            : demi_fuzz_campaign(CTX(h), &f.par, &cp, &lim, (demi_ext_event*)ev, DEMI_MAX_EXT_EVENTS, &res);
+  PUT_BYTES(events, ev, 0);
+  if (rc) return rc;
+  o[0] = (jlong)res.found; o[1] = (jlong)res.test_index; o[2] = (jlong)res.exec_index; o[3] = (jlong)res.n_events; o[4] = (jlong)res.tests_run;
+  o[5] = (jlong)res.launches; o[6] = (jlong)res.capacity_aborts;
+  o[7] = (jlong)((uint64_t)res.verdict.flags | ((uint64_t)res.verdict.fingerprint << 32)); o[8] = (jlong)res.verdict.hash;
+  SET_LONGS(result, 9, o);
+  return rc;
+}

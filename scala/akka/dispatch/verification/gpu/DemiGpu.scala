@@ -49,6 +49,24 @@ object DemiGpu {
    *  verdictsOrNull = long[2 * n * executions], flags = int[n] (bit 0 = some execution violates, bit 1 = some execution was aborted) */
   @native def randomExploreCandidates(h: Long, seedBase: Long, masks: Array[Long], executions: Int, limits: Array[Int],
                                       verdictsOrNull: Array[Long], flags: Array[Int]): Int
+  /** Fuzz campaigns.  A Fuzzer crosses the boundary as numEvents, prefix / postfixOrNull = byte[8 * n] (demi_ext_event), weightBits =
+   *  long[5] = doubleToRawLongBits of totalMass and the cumulative thresholds kill, + send, + partition, + unpartition (summed in
+   *  FuzzerWeights' own order), gen = byte[136] (demi_fuzz_send_gen: the MessageGenerator as 1..8 alternatives (msg_type, target, p0, p1)).
+   *  fuzzGenerate (demi_fuzz_generate): nTests tests, test i under new Random(seedBase + i) or seedsOrNull(i); they stay in the context;
+   *  eventsOrNull = byte[8 * nTests * stride] with stride = prefix + numEvents + postfix + 1, nEv = int[nTests], nBatchesOrNull = int[nTests] */
+  @native def fuzzGenerate(h: Long, numEvents: Int, prefix: Array[Byte], postfixOrNull: Array[Byte], weightBits: Array[Long], gen: Array[Byte],
+                           seedBase: Long, seedsOrNull: Array[Long], nTests: Int, eventsOrNull: Array[Byte], nEv: Array[Int],
+                           nBatchesOrNull: Array[Int]): Int
+  /** one RandomScheduler run of `executions` executions per test, a workgroup per test (demi_random_explore_tests): testsOrNull =
+   *  byte[8 * nTests * stride] with nEvOrNull = int[nTests], or null for the tests fuzzGenerate left in the context; verdictsOrNull =
+   *  long[2 * nTests * executions]; flags = int[nTests] (bit 0 = some execution violates, bit 1 = some execution was aborted) */
+  @native def randomExploreTests(h: Long, seedBase: Long, testsOrNull: Array[Byte], nEvOrNull: Array[Int], stride: Int, nTests: Int,
+                                 executions: Int, limits: Array[Int], verdictsOrNull: Array[Long], flags: Array[Int]): Int
+  /** RunnerUtils.fuzz's loop up to the first violating test (demi_fuzz_campaign): campaign = long[5] (test_seed_base, exec_seed_base,
+   *  executions_per_test, tests_per_launch, max_tests), events = byte[8 * 255] (the violating test), result = long[9] (found, test_index,
+   *  exec_index, n_events, tests_run, launches, capacity_aborts, verdict flags | fingerprint << 32, verdict hash) */
+  @native def fuzzCampaign(h: Long, numEvents: Int, prefix: Array[Byte], postfixOrNull: Array[Byte], weightBits: Array[Long], gen: Array[Byte],
+                           campaign: Array[Long], limits: Array[Int], events: Array[Byte], result: Array[Long]): Int
   @native def replayGetKept(h: Long, maskOrNull: Array[Long], skip: Int, limits: Array[Int], verdict: Array[Long], kept: Array[Byte]): Int
   /** the selectors of the execution replayLoad loaded (demi_replay_wildcard_load): typeSets = int[n recorded] (bit t = message type t
    *  matches, 0 = exact delivery), policies = byte[n recorded] (0 HEAD = SrcDstFIFOOnly, 1 FIRST = BackTrackStrategy / the timer wildcard,

@@ -28,30 +28,50 @@ import sys, os
 root, out = sys.argv[1], sys.argv[2]
 sys.path.insert(0, root); os.chdir(root)
 os.environ["DEMI_JIT_DUMP"] = out
+os.environ["DEMI_SPECIALIZE_CHECK_TESTS"] = "1"     # (the workgroup-per-test modules too, where the tree has them)
 from demi_amd import _native, model as M
 assert _native.__file__.startswith(root)
 _native.specialize_check(M.raft_model(5).to_struct())
 PY
 python "$G/dump.py" "$G/wt" "$G/jitA"; python "$G/dump.py" "$ROOT" "$G/jitB"
 python - "$G" <<'PY'
-import re, hashlib, sys, os, subprocess
+import re, hashlib, shutil, sys, os, subprocess
 G = sys.argv[1]
+# What is compared is the instructions.  Three things differ between two builds of the same code and are normalised: the
+# symbol's name inside branch-target annotations, the pc-relative displacement of a call into another function (the s_add_u32
+# behind s_getpc_b64: it moves when any function in between changes size) and the alignment padding behind the last instruction.
 def per(fn):
     d, cur = {}, None
     for l in open(fn):
         m = re.match(r'^[0-9a-f]+ <(.*)>:', l)
         if m: cur = m.group(1); d[cur] = []; continue
-        if cur and l.strip(): d[cur].append(re.sub(r'//.*', '', l).strip())
+        if cur and l.strip(): d[cur].append(re.sub(r'<[^>]*>', '', re.sub(r'//.*', '', l)).strip())
+    for v in d.values():
+        while v and (v[-1].startswith('s_nop') or v[-1] == '...'): v.pop()
+        for i in range(1, len(v)):
+            if v[i - 1].startswith('s_getpc_b64') and v[i].startswith('s_add_u32'): v[i] = re.sub(r'0x[0-9a-f]+$', 'REL', v[i])
     return {k: (hashlib.md5("\n".join(v).encode()).hexdigest()[:8], len(v)) for k, v in d.items() if k.startswith('_Z')}
-a, b = per(G + '/disA.txt'), per(G + '/disB.txt')
+# Kernels are matched by their demangled names with trailing defaulted template arguments dropped: a template that gained a
+# parameter (K1's TESTS) mangles every existing instantiation differently, and <..., false> is the old <...>.
+filt = shutil.which('llvm-cxxfilt') or shutil.which('c++filt') or '/opt/rocm/lib/llvm/bin/llvm-cxxfilt'
+def named(d):
+    names = list(d)
+    dem = subprocess.run([filt], input="\n".join(names), capture_output=True, text=True).stdout.split("\n")
+    out = {}
+    for k, n in zip(names, dem):
+        n = re.sub(r'k1_random_explore<([^>]*)>', lambda m: 'k1_random_explore<' + re.sub(r'(, false)+$', '', m.group(1)) + '>', n)
+        out[re.sub(r'K1ArgsOf<[^>]*>::type', 'K1ArgsOf::type', n)] = d[k]
+    return out
+a, b = named(per(G + '/disA.txt')), named(per(G + '/disB.txt'))
 for k in sorted(set(a) | set(b)):
-    print("generic     %s %-78s %s -> %s" % ("SAME" if a.get(k) == b.get(k) else "DIFF", k[:78], a.get(k, ("-", 0))[1], b.get(k, ("-", 0))[1]))
-for k in range(16):
+    st = "SAME" if a.get(k) == b.get(k) else "NEW " if k not in a else "GONE" if k not in b else "DIFF"
+    print("generic     %s %-110s %s -> %s" % (st, k[:110], a.get(k, ("-", 0))[1], b.get(k, ("-", 0))[1]))
+for k in range(64):          # (every module either tree dumped: demi_gpu.hip JK_COUNT)
     h = []
     for t in "AB":
         p = "%s/jit%s.%d" % (G, t, k)
         if not os.path.exists(p): h.append(None); continue
         subprocess.check_call(["/opt/rocm/lib/llvm/bin/llvm-objcopy", "-O", "binary", "--only-section=.text", p, p + ".text"])
         h.append(hashlib.md5(open(p + ".text", "rb").read()).hexdigest()[:8])
-    if h[0] or h[1]: print("specialised %s kernel %d (raft5) %s -> %s" % ("SAME" if h[0] == h[1] else "DIFF", k, h[0], h[1]))
+    if h[0] or h[1]: print("specialised %s kernel %d (raft5) %s -> %s" % ("SAME" if h[0] == h[1] else "NEW " if not h[0] else "GONE" if not h[1] else "DIFF", k, h[0], h[1]))
 PY
