@@ -20,7 +20,8 @@ EXPORTS = ["demi_ctx_create", "demi_ctx_destroy", "demi_last_error", "demi_versi
            "demi_comm_allgather_dev", "demi_random_explore_sharded", "demi_replay_batch_sharded", "demi_abi_version", "demi_replay_externals_len", "demi_edit_distance_dpor_ddmin", "demi_dpor_explored", "demi_random_ddmin", "demi_random_explore_candidates", "demi_ext_payload_areas",
            "demi_replay_wildcard_load", "demi_replay_wildcard_batch", "demi_replay_wildcard_get_trace",
            "demi_replay_wildcard_candidates", "demi_wildcard_ddmin",
-           "demi_fuzz_stride", "demi_fuzz_generate", "demi_random_explore_tests", "demi_fuzz_campaign"]
+           "demi_fuzz_stride", "demi_fuzz_generate", "demi_random_explore_tests", "demi_fuzz_campaign",
+           "demi_replay_removal_round", "demi_minimize_internals"]
 
 _lib = None
 ALLGATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t)     # demi_allgather_fn
@@ -149,6 +150,10 @@ def lib():
                                             C.c_void_p, C.c_void_p]
     L.demi_fuzz_campaign.argtypes = [C.c_void_p, C.POINTER(T.FuzzParams), C.POINTER(T.FuzzCampaignParams), C.POINTER(T.Limits), C.c_void_p,
                                      C.c_uint32, C.POINTER(T.FuzzCampaignResult)]
+    L.demi_replay_removal_round.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(T.Limits), C.c_void_p,
+                                            C.POINTER(T.RemovalRoundResult)]
+    L.demi_minimize_internals.argtypes = [C.c_void_p, C.POINTER(T.Limits), C.POINTER(T.IntminParams), C.c_void_p, C.c_uint32,
+                                          C.POINTER(C.c_uint32), C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.POINTER(T.IntminStats)]
     # every export has its argument types declared: an undeclared one would silently truncate pointers to 32 bits
     for name in EXPORTS:
         fn = getattr(L, name)
@@ -470,6 +475,40 @@ class Context:
         self._check(lib().demi_replay_get_kept(self._h, mp, C.c_uint32(int(skip) & 0xFFFFFFFF), C.byref(limits),
                                                C.byref(v), kept.ctypes.data))
         return v, kept[:int(n_rec)]
+
+    def replay_removal_round(self, skips, limits, mask=None):
+        """One round of STSSchedMinimizer.minimize (demi_replay_removal_round): the proposals `skips` over the loaded execution,
+        reduced on the device.  (RemovalRoundResult, uint8[n_rec] kept marks of proposal first_hit - None without a hit)."""
+        import numpy as np
+        skips = np.ascontiguousarray(skips, dtype=np.uint32)
+        mp = None
+        if mask is not None:
+            mask = np.ascontiguousarray(mask, dtype=np.uint64).reshape(4)
+            mp = mask.ctypes.data
+        n_rec = int(lib().demi_replay_recorded_len(self._h))
+        kept = np.zeros(max(n_rec, 1), dtype=np.uint8)
+        res = T.RemovalRoundResult()
+        self._check(lib().demi_replay_removal_round(self._h, mp, skips.ctypes.data if len(skips) else None, len(skips), C.byref(limits),
+                                                    kept.ctypes.data, C.byref(res)))
+        return res, (kept[:n_rec] if res.first_hit != 0xFFFFFFFF else None)
+
+    def minimize_internals(self, limits, params=None, cap=None):
+        """RunnerUtils.minimizeInternals on the loaded replay, natively (demi_minimize_internals): (minimized recorded events,
+        record_internal_size sequence, candidates per round, IntminStats).  The context's loaded execution is the minimized one
+        afterwards - also when the call raises on a capacity (then the last adopted trace)."""
+        import numpy as np
+        params = params or T.IntminParams()
+        n_rec = int(lib().demi_replay_recorded_len(self._h))
+        cap = n_rec if cap is None else int(cap)
+        out = np.zeros(max(cap, 1), dtype=T.REC_EVENT_DTYPE)
+        sizes = np.zeros(max(n_rec, 1), dtype=np.uint32)       # (a replay per delivery at the most)
+        batches = np.zeros(max(n_rec, 1), dtype=np.uint32)
+        n = C.c_uint32(0)
+        st = T.IntminStats()
+        self._check(lib().demi_minimize_internals(self._h, C.byref(limits), C.byref(params), out.ctypes.data, cap, C.byref(n),
+                                                  sizes.ctypes.data, len(sizes), batches.ctypes.data, len(batches), C.byref(st)))
+        return out[:n.value].copy(), [int(x) for x in sizes[:min(len(sizes), st.total_replays)]], \
+            [int(x) for x in batches[:min(len(batches), st.rounds)]], st
 
     def replay_wildcard_load(self, type_sets, policies):
         """The selector of every recorded event of the loaded execution (demi_replay_wildcard_load): type_sets uint32[n_rec]

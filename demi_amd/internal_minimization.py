@@ -267,6 +267,27 @@ class StsRemovalOracle:
             return None
         return executed_trace(trace, kept)
 
+    def minimize_native(self, mcs: np.ndarray, verified_mcs: EventTrace, violation: ViolationFingerprint,
+                        removalStrategy: RemovalStrategy, stats: Optional["MinimizationStats"] = None,
+                        max_batch: int = 1 << 14) -> Tuple["MinimizationStats", EventTrace]:
+        """STSSchedMinimizer(...).minimize() as one call of the library (demi_minimize_internals).  Only the class of
+        `removalStrategy` is used: the library builds the strategy's state from the loaded execution itself."""
+        if type(removalStrategy) is LeftToRightOneAtATime:
+            code = T.REMOVAL_LEFT_TO_RIGHT
+        elif type(removalStrategy) is SrcDstFIFORemoval:
+            code = T.REMOVAL_SRC_DST_FIFO
+        else:
+            raise ValueError("native internal minimization knows LeftToRightOneAtATime and SrcDstFIFORemoval, not %s"
+                             % type(removalStrategy).__name__)
+        stats = stats or MinimizationStats()
+        self._ctx.replay_load(mcs, verified_mcs.events)
+        # the call replaces the context's loaded execution (also when it raises): the cache no longer says what is loaded
+        self._loaded = None
+        events, sizes, batches, st = self._ctx.minimize_internals(self._limits(violation), T.IntminParams(code, max(1, int(max_batch))))
+        stats.increment_replays(int(st.total_replays))
+        self.native_stats, self.native_sizes, self.native_batches = st, sizes, batches
+        return stats, EventTrace(events, mcs)
+
     def shutdown(self):
         self._ctx.close()
 
@@ -340,15 +361,18 @@ class STSSchedMinimizer:
 def minimizeInternals(schedulerConfig: SchedulerConfig, mcs: np.ndarray, verified_mcs: EventTrace,
                       violation: ViolationFingerprint, removalStrategyCtor=None, oracle=None,
                       stats: Optional[MinimizationStats] = None, device: int = 0, p_max: int = 64,
-                      max_batch: int = 1 << 14) -> Tuple[MinimizationStats, EventTrace]:
+                      max_batch: int = 1 << 14, native: bool = False) -> Tuple[MinimizationStats, EventTrace]:
     """RunnerUtils.minimizeInternals (RunnerUtils.scala:980-1003).  pre: replaying verified_mcs reproduces the
-    violation.  removalStrategyCtor == None uses LeftToRightOneAtATime."""
+    violation.  removalStrategyCtor == None uses LeftToRightOneAtATime.  native: the whole loop as ONE call of the library
+    (demi_minimize_internals: same result, same total_replays; the strategy must be one of the two OneAtATime strategies)."""
     strategy = LeftToRightOneAtATime(verified_mcs, schedulerConfig.model) if removalStrategyCtor is None \
         else removalStrategyCtor()
     own = oracle is None
     if own:
         oracle = StsRemovalOracle(schedulerConfig, device=device, p_max=p_max)
     try:
+        if native:
+            return oracle.minimize_native(mcs, verified_mcs, violation, strategy, stats=stats, max_batch=max_batch)
         return STSSchedMinimizer(mcs, verified_mcs, violation, strategy, oracle, stats=stats,
                                  max_batch=max_batch).minimize()
     finally:

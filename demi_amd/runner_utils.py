@@ -269,13 +269,13 @@ class _WildcardSpeculativeDDMin(SpeculativeDDMin):
 
 def run_the_gamut(schedulerConfig: SchedulerConfig, trace: EventTrace, violation: ViolationFingerprint,
                   stages: Sequence[str] = ("DDMin", "IntMin"), device: int = 0, p_max: int = 64,
-                  shouldRerunDDMin: Callable[[np.ndarray], bool] = lambda externals: True):
+                  shouldRerunDDMin: Callable[[np.ndarray], bool] = lambda externals: True, native_intmin: bool = False):
     """The stages of RunnerUtils.runTheGamut (:165-380) that run on the GPU path, in the reference's order:
     stsSchedDDMin (external events), then minimizeInternals with LeftToRightOneAtATime, then - only when named in `stages` -
     "WildCardDDMinNoBacktracks" and "WildCardDDMinLastOnly" (wildcardDDMin over the current trace, :363-411, guarded by
     shouldRerunDDMin as there), then "WildcardsNoBackTracks" and "WildcardsLastOnly" (wildcard_minimization.WildcardMinimizer, ClockClusterizer).  Returns a dict with the MCS
     (indices into trace.original_externals), the verified MCS execution, the internally minimized execution and the
-    replay counts of each stage."""
+    replay counts of each stage.  native_intmin: the internal minimization as one native call (demi_minimize_internals)."""
     from .internal_minimization import countMsgEvents, minimizeInternals
     from .minification import stsSchedDDMin
     from .schedulers import STSScheduler
@@ -295,7 +295,7 @@ def run_the_gamut(schedulerConfig: SchedulerConfig, trace: EventTrace, violation
     if "IntMin" in stages and cur_trace is not None:
         stats = MinimizationStats()
         _, minimized = minimizeInternals(schedulerConfig, cur_trace.original_externals, cur_trace, violation, stats=stats,
-                                         device=device, p_max=p_max)
+                                         device=device, p_max=p_max, native=native_intmin)
         out.update(intmin_replays=stats.total_replays, minimized=minimized, minimized_deliveries=countMsgEvents(minimized))
         cur_trace = minimized
     # wildcard DDMin over the externals, opt-in, as RunnerUtils.scala:363-411 places and configures it: without backtracks (the

@@ -210,6 +210,31 @@ class DdminStats(C.Structure):
                 ("replays", C.c_uint64)]
 
 
+REMOVAL_LEFT_TO_RIGHT = 0     # demi_removal_strategy
+REMOVAL_SRC_DST_FIFO = 1
+
+
+class RemovalRoundResult(C.Structure):
+    """demi_removal_round_result"""
+    _fields_ = [("first_hit", C.c_uint32), ("n_kept", C.c_uint32), ("retried", C.c_uint32), ("launches", C.c_uint32),
+                ("verdict", Verdict)]
+
+
+class IntminParams(C.Structure):
+    """demi_intmin_params"""
+    _fields_ = [("strategy", C.c_uint32), ("max_batch", C.c_uint32)]
+
+    def __init__(self, strategy=REMOVAL_LEFT_TO_RIGHT, max_batch=0):
+        super().__init__(strategy, max_batch)
+
+
+class IntminStats(C.Structure):
+    """demi_intmin_stats"""
+    _fields_ = [("total_replays", C.c_uint64), ("replays_run", C.c_uint64), ("rounds", C.c_uint32), ("launches", C.c_uint32),
+                ("adoptions", C.c_uint32), ("retried", C.c_uint32), ("unignorable", C.c_uint32), ("deliveries_before", C.c_uint32),
+                ("deliveries_after", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 class WildcardDdminResult(C.Structure):
     """demi_wildcard_ddmin_result"""
     _fields_ = [("total_replays", C.c_uint64), ("proposals_run", C.c_uint64), ("mcs_evaluated", C.c_uint32), ("mcs_first_hit", C.c_uint32),

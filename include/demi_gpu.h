@@ -465,6 +465,70 @@ uint32_t demi_replay_recorded_len(const demi_ctx* ctx);
 /* Number of external events of that execution (0 without one): the length demi_ddmin's `conjoined` must have. */
 uint32_t demi_replay_externals_len(const demi_ctx* ctx);
 
+/* One ROUND of STSSchedMinimizer.minimize (ScheduleCheckers.scala:50-57 around RunnerUtils.testWithStsSched, RunnerUtils.scala:
+ * 913-943): the strategy's upcoming proposals skip[0..n) - each assuming the one before it failed - replayed in one launch that
+ * also writes every candidate's executed-trace marks, and reduced ON THE DEVICE to what the sequential loop needs: the first
+ * proposal that still triggers the violation and its executed trace.  It replaces demi_replay_removal_batch, the host's search
+ * through n verdicts and the second replay of the winner by demi_replay_get_kept; the host reads one record and one row of marks.
+ *   mask      [4] or NULL: ONE subsequence of the externals for all candidates (NULL keeps every external);
+ *   first_hit the lowest i for which demi_replay_removal_batch reports DEMI_V_VIOLATION, 0xFFFFFFFF = none (also for n = 0);
+ *   verdict / out_kept [demi_replay_recorded_len]: byte for byte what demi_replay_get_kept(mask, skip[first_hit]) returns
+ *             (verdict all zero and out_kept untouched without a hit);  n_kept = marks set in out_kept.
+ * A candidate whose replay is aborted on a capacity (DEMI_V_PENDING_OVF / DEMI_V_QUEUE_OVF) BEFORE the first hit - anywhere when
+ * there is no hit - is no answer: the proposals up to the hit are evaluated again with p_max = DEMI_MAX_PENDING (`retried`
+ * counts them), and DEMI_ERR_CAPACITY is returned if an abort remains - never "does not reproduce".  An abort after the first
+ * hit is irrelevant: the sequential loop never gets there.
+ * The marks of a launch's candidates occupy n x (lowered events) bytes of device memory; a round wider than the budget of
+ * 64 MiB (the widest round of a DEMI_MAX_REC_EVENTS trace at max_batch 4096; experiment knob DEMI_INTMIN_KEPT_BYTES) runs as
+ * consecutive launches in proposal order and stops at the first launch that holds a hit.  `launches` counts replay launches. */
+typedef struct {
+  uint32_t first_hit;
+  uint32_t n_kept;
+  uint32_t retried;
+  uint32_t launches;
+  demi_verdict verdict;
+} demi_removal_round_result;   /* 32 bytes */
+int demi_replay_removal_round(demi_ctx* ctx, const uint64_t* mask /* [4] or NULL */, const uint32_t* skip /* [n] */, uint32_t n,
+                              const demi_limits* limits, uint8_t* out_kept /* [n_rec] */, demi_removal_round_result* result);
+
+/* ---------------------------------------------------------- internal-event minimization in one call
+ * Replaces RunnerUtils.minimizeInternals (RunnerUtils.scala:980-1003): STSSchedMinimizer.minimize (ScheduleCheckers.scala:35-107)
+ * with a OneAtATimeStrategy (OneAtATimeRemoval.scala:17-131) - LeftToRightOneAtATime (:134-139) or SrcDstFIFORemoval (:141-251) -
+ * over the execution loaded by demi_replay_load: the verified MCS execution with the MCS as its externals (every external is
+ * kept: test(mcs)).  A delivery is identified by (snd, rcv, msg_type, p0, p1, p_hi); deliveries of the table's external messages
+ * (msg_class DEMI_MSG_EXTERNAL) are unignorable (:32-35).  Per round up to max_batch upcoming proposals are enumerated on a clone
+ * of the strategy and evaluated by demi_replay_removal_round; the strategy is then advanced by the calls the sequential loop
+ * would have made, so the result, total_replays and the record_internal_size sequence are the sequential algorithm's
+ * (demi_amd/internal_minimization.py is the same walk in Python).
+ *   out_trace [cap]: the minimized execution (lastFailingTrace), *out_n its length;
+ *   out_sizes [sizes_cap] (may be NULL): MinimizationStats.record_internal_size after every sequential replay (total_replays entries);
+ *   out_batches [batches_cap] (may be NULL): candidates per round (`rounds` entries).
+ * THE LOADED EXECUTION CHANGES: on return the context holds the minimized execution, as if the caller had called
+ * demi_replay_load(externals, out_trace) - also when DEMI_ERR_CAPACITY is returned, for a replay that does not fit or an out_trace
+ * that is too small (the message names the length needed): the last adopted trace is loaded.
+ * limits as for demi_replay_removal_batch (filter_known_absents included).  DEMI_ERR_INVALID_ARG ("single rank") with a
+ * communicator attached: rounds are not sharded.  BeginUnignorableEvents blocks and StateMachineRemoval are not built. */
+typedef enum { DEMI_REMOVAL_LEFT_TO_RIGHT = 0, DEMI_REMOVAL_SRC_DST_FIFO = 1 } demi_removal_strategy;
+typedef struct {
+  uint32_t strategy;         /* demi_removal_strategy */
+  uint32_t max_batch;        /* proposals per round: 0 = 16384; 1 = the reference's one-replay-at-a-time loop */
+} demi_intmin_params;
+typedef struct {
+  uint64_t total_replays;    /* MinimizationStats.total_replays: the replays of the sequential loop */
+  uint64_t replays_run;      /* candidates replayed on the device, speculation and retries included */
+  uint32_t rounds;           /* demi_replay_removal_round calls */
+  uint32_t launches;         /* replay launches (= rounds unless a round was split or evaluated again) */
+  uint32_t adoptions;        /* removals that still triggered the violation */
+  uint32_t retried;          /* candidates evaluated again with the largest pending set */
+  uint32_t unignorable;      /* RemovalStrategy.unignorable */
+  uint32_t deliveries_before, deliveries_after;   /* countMsgEvents of the loaded / the minimized execution */
+  uint32_t reserved;
+} demi_intmin_stats;         /* 48 bytes */
+int demi_minimize_internals(demi_ctx* ctx, const demi_limits* limits, const demi_intmin_params* params,
+                            demi_rec_event* out_trace /* [cap] */, uint32_t cap, uint32_t* out_n,
+                            uint32_t* out_sizes /* [sizes_cap] or NULL */, uint32_t sizes_cap,
+                            uint32_t* out_batches /* [batches_cap] or NULL */, uint32_t batches_cap, demi_intmin_stats* stats);
+
 /* ---------------------------------------------------------- K2W: the replay oracle of the wildcard minimizers
  * WildcardMinimizer (minification/wildcard_minimization/WildcardMinimizer.scala) with TestScheduler.STSSched: a Clusterizer
  * proposes traces over the SAME original trace in which every kept internal or timer delivery is a

@@ -284,6 +284,60 @@ JNIEXPORT jint JNICALL FN(replayGetKept)(JNIEnv* e, jclass c, jlong h, jlongArra
   SET_LONGS(verdict, 2, (const jlong*)(const void*)&v);
   return rc;
 }
+/* One round of STSSchedMinimizer.minimize (demi_replay_removal_round).  kept: byte[>= recorded events of the loaded execution];
+ * result: long[6] = first_hit (-1: none), n_kept, retried, launches, then the winner's verdict as its two words */
+JNIEXPORT jint JNICALL FN(replayRemovalRound)(JNIEnv* e, jclass c, jlong h, jlongArray maskOrNull, jintArray skip, jintArray limits,
+                                             jbyteArray kept, jlongArray result) {
+  demi_limits lim;
+  demi_removal_round_result res;
+  (void)c;
+  if (limits_of(e, limits, &lim) || LEN(skip) < 0 || LEN(kept) < 0 || LEN(result) != 6 || (maskOrNull && LEN(maskOrNull) != 4)) return DEMI_ERR_INVALID_ARG;
+  if ((uint64_t)LEN(kept) < (uint64_t)demi_replay_recorded_len(CTX(h))) return DEMI_ERR_CAPACITY;
+  memset(&res, 0, sizeof res);
+  void* m = LONGS(maskOrNull);
+  void* s = INTS(skip);
+  void* k = BYTES(kept);
+  jint rc = (LOST(maskOrNull, m) || LOST(skip, s) || LOST(kept, k)) ? DEMI_ERR_INVALID_ARG
+            : demi_replay_removal_round(CTX(h), (const uint64_t*)m, (const uint32_t*)s, (uint32_t)LEN(skip), &lim, (uint8_t*)k, &res);
+  PUT_BYTES(kept, k, 0);
+  PUT_INTS(skip, s, JNI_ABORT);
+  PUT_LONGS(maskOrNull, m, JNI_ABORT);
+  jlong r[6];
+  r[0] = (jlong)(int32_t)res.first_hit; r[1] = (jlong)res.n_kept; r[2] = (jlong)res.retried; r[3] = (jlong)res.launches;
+  memcpy(&r[4], &res.verdict, sizeof res.verdict);
+  SET_LONGS(result, 6, r);
+  return rc;
+}
+/* RunnerUtils.minimizeInternals in one call (demi_minimize_internals) on the execution replayLoad loaded; the loaded execution is the
+ * minimized one afterwards.  params: int[2] = strategy (0 LeftToRightOneAtATime, 1 SrcDstFIFORemoval), max_batch; trace: byte[16 * cap]
+ * receives the minimized recorded events; sizesOrNull: int[] the record_internal_size sequence; stats: long[10] = events of the result,
+ * total_replays, replays_run, rounds, launches, adoptions, retried, unignorable, deliveries_before, deliveries_after */
+JNIEXPORT jint JNICALL FN(minimizeInternals)(JNIEnv* e, jclass c, jlong h, jintArray limits, jintArray params, jbyteArray trace,
+                                            jintArray sizesOrNull, jlongArray stats) {
+  demi_limits lim;
+  demi_intmin_params par;
+  demi_intmin_stats st;
+  jint pr[2];
+  uint32_t n = 0;
+  (void)c;
+  if (limits_of(e, limits, &lim) || LEN(params) != 2 || LEN(trace) < 0 || LEN(stats) != 10) return DEMI_ERR_INVALID_ARG;
+  (*e)->GetIntArrayRegion(e, params, 0, 2, pr);
+  par.strategy = (uint32_t)pr[0]; par.max_batch = (uint32_t)pr[1];
+  memset(&st, 0, sizeof st);
+  void* t = BYTES(trace);
+  void* z = INTS(sizesOrNull);
+  jint rc = (LOST(trace, t) || LOST(sizesOrNull, z)) ? DEMI_ERR_INVALID_ARG
+            : demi_minimize_internals(CTX(h), &lim, &par, (demi_rec_event*)t, (uint32_t)(LEN(trace) / (jint)sizeof(demi_rec_event)), &n,
+                                      (uint32_t*)z, sizesOrNull ? (uint32_t)LEN(sizesOrNull) : 0u, NULL, 0, &st);
+  PUT_INTS(sizesOrNull, z, 0);
+  PUT_BYTES(trace, t, 0);
+  jlong o[10];
+  o[0] = (jlong)n; o[1] = (jlong)st.total_replays; o[2] = (jlong)st.replays_run; o[3] = (jlong)st.rounds; o[4] = (jlong)st.launches;
+  o[5] = (jlong)st.adoptions; o[6] = (jlong)st.retried; o[7] = (jlong)st.unignorable; o[8] = (jlong)st.deliveries_before;
+  o[9] = (jlong)st.deliveries_after;
+  SET_LONGS(stats, 10, o);
+  return rc;
+}
 
 /* ---- K2W: the replay oracle of the wildcard minimizers (demi_replay_wildcard_*).  typeSets: int[n recorded], policies: byte[n recorded]
  *      (n = demi_replay_recorded_len of the execution replayLoad loaded; shorter arrays are refused) */

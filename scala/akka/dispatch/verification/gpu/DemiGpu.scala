@@ -68,6 +68,15 @@ object DemiGpu {
   @native def fuzzCampaign(h: Long, numEvents: Int, prefix: Array[Byte], postfixOrNull: Array[Byte], weightBits: Array[Long], gen: Array[Byte],
                            campaign: Array[Long], limits: Array[Int], events: Array[Byte], result: Array[Long]): Int
   @native def replayGetKept(h: Long, maskOrNull: Array[Long], skip: Int, limits: Array[Int], verdict: Array[Long], kept: Array[Byte]): Int
+  /** one round of STSSchedMinimizer.minimize, reduced on the device (demi_replay_removal_round): skip = the strategy's upcoming proposals,
+   *  kept = byte[n recorded] (the executed-trace marks of proposal first_hit), result = long[6] (first_hit or -1, n_kept, retried, launches,
+   *  the winner's two verdict words) */
+  @native def replayRemovalRound(h: Long, maskOrNull: Array[Long], skip: Array[Int], limits: Array[Int], kept: Array[Byte], result: Array[Long]): Int
+  /** RunnerUtils.minimizeInternals in one call (demi_minimize_internals) on the execution replayLoad loaded, which is the minimized one
+   *  afterwards: params = int[2] (strategy: 0 LeftToRightOneAtATime, 1 SrcDstFIFORemoval; max_batch), trace = byte[16 * cap] (the minimized
+   *  recorded events), sizesOrNull = int[] (record_internal_size per replay), stats = long[10] (events of the result, total_replays,
+   *  replays_run, rounds, launches, adoptions, retried, unignorable, deliveries_before, deliveries_after) */
+  @native def minimizeInternals(h: Long, limits: Array[Int], params: Array[Int], trace: Array[Byte], sizesOrNull: Array[Int], stats: Array[Long]): Int
   /** the selectors of the execution replayLoad loaded (demi_replay_wildcard_load): typeSets = int[n recorded] (bit t = message type t
    *  matches, 0 = exact delivery), policies = byte[n recorded] (0 HEAD = SrcDstFIFOOnly, 1 FIRST = BackTrackStrategy / the timer wildcard,
    *  2 LAST = LastOnlyStrategy) */

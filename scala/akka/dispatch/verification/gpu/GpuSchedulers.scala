@@ -338,6 +338,24 @@ class GpuStsRemovalOracle(schedulerConfig: SchedulerConfig, mcs: Seq[ExternalEve
     if ((flags(v, 0) & V_VIOLATION) == 0) None
     else { val t = new EventTrace(trace.original_externals); for ((e, k) <- trace.events.zip(kept) if k != 0) t += e; Some(t) }
   }
+  /** RunnerUtils.minimizeInternals (RunnerUtils.scala:980-1003) / STSSchedMinimizer.minimize (ScheduleCheckers.scala:35-107) in ONE call
+   *  of the library (demi_minimize_internals) instead of the loop around testRemovals / executed: `strategy` is 0 for
+   *  LeftToRightOneAtATime, 1 for SrcDstFIFORemoval.  Returns (MinimizationStats.total_replays, the minimized trace, the
+   *  record_internal_size sequence).  The context's loaded execution is the minimized one afterwards, so `loaded` is forgotten. */
+  def minimizeInternals(verifiedMcs: EventTrace, fp: ViolationFingerprint, strategy: Int, maxBatch: Int = 0): (Long, EventTrace, Array[Int]) = {
+    load(verifiedMcs)
+    loaded = null
+    val packed = FlatEvents.packRecorded(verifiedMcs, lowering)
+    val out = new Array[Byte](packed.length); val sizes = new Array[Int](packed.length / 16 + 1); val st = new Array[Long](10)
+    check(h, DemiGpu.minimizeInternals(h, limits(fp), Array(strategy, maxBatch), out, sizes, st))
+    // the result is a subsequence of the packed records, byte for byte: pair them up in order
+    val t = new EventTrace(verifiedMcs.original_externals)
+    var o = 0
+    for ((e, i) <- verifiedMcs.events.zipWithIndex if o < st(0).toInt)
+      if (java.util.Arrays.equals(java.util.Arrays.copyOfRange(packed, 16 * i, 16 * i + 16), java.util.Arrays.copyOfRange(out, 16 * o, 16 * o + 16))) { t += e; o += 1 }
+    if (o != st(0).toInt) throw new IllegalStateException("the minimized trace is not a subsequence of the verified MCS trace")
+    (st(1), t, sizes.take(st(1).toInt))
+  }
   def shutdown() { ctxDestroy(h) }
 }
 
