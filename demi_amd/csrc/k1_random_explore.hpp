@@ -59,15 +59,15 @@ struct K1MultiArgs : K1Args {
 // SPREAD variant (round 6): a launch far smaller than the chip on as many waves as it has executions.  A wave's iteration costs what
 // the UNION of its lanes' paths costs (~780 vector instructions with 56 lanes delivering, ~240 for a lane alone: DESIGN section 4
 // K1), so a launch of 100 executions is faster as 100 waves of one lane than as two full waves.  Only the first lanes_per_wave
-// lanes of a wave ever claim work; the others idle through the wave's cooperative steps.  Its own struct and its own template
-// parameter: every other variant keeps its kernel-argument segment and its instructions.
+// lanes of a wave ever claim work; the others idle through the wave's cooperative steps.  Its own struct and its own K1Variant
+// value: every other variant keeps its kernel-argument segment and its instructions.
 struct K1SpreadArgs : K1Args {
   uint32_t lanes_per_wave;      // 1 .. 64
 };
 // TESTS variant (demi_random_explore_tests, the fuzz campaign): workgroup = one TEST of an array of external traces, e.g. the ones
 // k_fuzz_generate left on the device.  MULTI compacts a mask of the one loaded trace at that point; this front end copies the
 // workgroup's own trace into LDS instead, and from there the variant runs as MULTI does.  `n_ev` and `n_batches` of K1Args are
-// the launch's largest (they size the LDS), `trace` is unused.  Its own struct and template parameter, for SPREAD's reason.
+// the launch's largest (they size the LDS), `trace` is unused.  Its own struct and K1Variant value, for SPREAD's reason.
 struct K1TestsArgs : K1Args {
   const uint64_t* tests;        // [n_tests][stride] demi_ext_event as 8-byte words
   const uint32_t* test_n_ev;    // [n_tests] a test's length, <= n_ev <= stride
@@ -77,10 +77,12 @@ struct K1TestsArgs : K1Args {
   uint32_t* test_flags;         // [n_tests], zeroed by the host: bit 0 = some execution violated, bit 1 = some execution aborted on a capacity
   uint32_t lanes_per_wave;      // 0 = 64; as in K1MultiArgs
 };
-template <bool MULTI, bool SPREAD = false, bool TESTS = false> struct K1ArgsOf { typedef K1Args type; };
-template <> struct K1ArgsOf<true, false, false> { typedef K1MultiArgs type; };
-template <> struct K1ArgsOf<false, true, false> { typedef K1SpreadArgs type; };
-template <> struct K1ArgsOf<false, false, true> { typedef K1TestsArgs type; };
+// The four front ends exclude each other, so they are one template parameter: a kernel is <REC, FIFO, CARRY, variant>.
+enum K1Variant { K1_PLAIN, K1_REBIN, K1_MULTI, K1_SPREAD, K1_TESTS };
+template <K1Variant V> struct K1ArgsOf { typedef K1Args type; };
+template <> struct K1ArgsOf<K1_MULTI> { typedef K1MultiArgs type; };
+template <> struct K1ArgsOf<K1_SPREAD> { typedef K1SpreadArgs type; };
+template <> struct K1ArgsOf<K1_TESTS> { typedef K1TestsArgs type; };
 
 enum : int { PH_IDLE = 0, PH_INJECT = 1, PH_DISPATCH = 2, PH_FINISH = 3 };
 
@@ -207,12 +209,12 @@ __host__ __device__ inline size_t k1_lds_bytes(uint32_t code_len, uint32_t n_ev,
 // TESTS (demi_random_explore_tests): MULTI's shape over an ARRAY of traces - workgroup group i copies test i into LDS, lane k runs
 // its execution k, a violating execution sets the test's flag.  Verdict i * epc + k is what the plain kernel returns for
 // trace_load(test i) and seed_base + k.
-template <bool REC, bool FIFO = false, bool CARRY = false, bool REBIN = false, bool MULTI = false, bool SPREAD = false, bool TESTS = false>
-__global__ K1_LAUNCH_BOUNDS void k1_random_explore(const typename K1ArgsOf<MULTI, SPREAD, TESTS>::type args) {
-  static_assert(!TESTS || (!REC && !CARRY && !REBIN && !MULTI && !SPREAD), "a batch of tests runs the non-recording, per-execution-seed kernel");
-  static_assert(!SPREAD || (!REC && !CARRY && !REBIN && !MULTI), "the spread variant is the plain per-execution kernel");
-  static_assert(!REBIN || (!REC && !FIFO), "the re-binned kernel exists for the non-recording FullyRandom variant");
-  static_assert(!MULTI || (!REC && !CARRY && !REBIN), "a frontier of candidates runs the non-recording, per-execution-seed kernel");
+template <bool REC, bool FIFO = false, bool CARRY = false, K1Variant V = K1_PLAIN>
+__global__ K1_LAUNCH_BOUNDS void k1_random_explore(const typename K1ArgsOf<V>::type args) {
+  constexpr bool REBIN = V == K1_REBIN, MULTI = V == K1_MULTI, SPREAD = V == K1_SPREAD, TESTS = V == K1_TESTS;
+  static_assert(V == K1_PLAIN || !REC, "every variant but the plain kernel is a non-recording one");
+  static_assert(V == K1_PLAIN || V == K1_REBIN || !CARRY, "MULTI, SPREAD and TESTS run the per-execution-seed kernel");
+  static_assert(!REBIN || !FIFO, "the re-binned kernel exists for the non-recording FullyRandom variant");
   static_assert(!BIG_TU || !REBIN, "the re-binned kernel packs an 8 x 8 reach row: tables of up to 8 actors");
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   Tables t;

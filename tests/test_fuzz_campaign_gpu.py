@@ -167,6 +167,25 @@ def test_tests_launch_equals_the_plain_path_and_the_oracle(raft5_ctx, monkeypatc
     assert not (f & 2).any()
 
 
+@pytest.mark.parametrize("specialize", [False, True])
+def test_more_executions_per_test_than_a_workgroup_holds(raft5_ctx, monkeypatch, specialize):
+    """epc = 300: with full waves (64 lanes) a test is two workgroups, the second with 44 of its 256 lanes at work; with the lanes
+    per wave the launch picks itself, as many workgroups as 300 executions need at that width."""
+    epc = 300 if not EMU else 70
+    tests = [FC.k1_tests()[i] for i in (0, 16, 32)]
+    lim = FC.k1_limits()
+    ctx = raft5_ctx(specialize)
+    plain = _plain_path(ctx, specialize, "epc300", epc, tests, lim)
+    for lanes in (None, 64) if not EMU else (16,):
+        if lanes:
+            monkeypatch.setenv("DEMI_K1_LANES_PER_WAVE", str(lanes))
+        v, f = ctx.random_explore_tests(tests, epc, lim, seed_base=FC.K1_SEED_BASE)
+        assert v.shape == (3, epc)
+        for i in range(3):
+            assert v[i].tobytes() == plain[i].tobytes(), (lanes, i)
+            assert int(f[i]) == (1 if (plain[i]["flags"] & T.V_VIOLATION).any() else 0) | (2 if (plain[i]["flags"] & OVF).any() else 0), (lanes, i)
+
+
 def test_resident_tests_are_what_the_host_array_is(raft5_ctx):
     """tests = NULL: the generated tests in the context, explored without ever leaving the device"""
     cfg, n, epc = FC.K1_KILLS5, 21 if not EMU else 5, 20

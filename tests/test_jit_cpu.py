@@ -722,3 +722,66 @@ def test_committed_k1_counters_describe_the_kernel_this_tree_compiles(tmp_path):
         prof = json.load(f)
     assert prof.get("code_id") == here, ("profiles/k1_counters.json was taken on code id %s, this tree compiles %s: "
                                          "re-run tools/profile_r5.sh on the GPU box and commit its k1_counters.json" % (prof.get("code_id"), here))
+
+
+# The module numbers of the kernels demi_model_specialize compiles (demi_gpu.hip kJit): DEMI_JIT_DUMP / DEMI_JIT_DUMP_SRC write
+# <path>.<number>, tools/ read them by number.  Per number the last line of the translation unit handed to hiprtc: the explicit
+# instantiation of a K1 variant, or the header of the kernels that are no templates.
+_K1_INST = "template __global__ void demi::k1_random_explore<%s>(const demi::%s);"
+JIT_MODULES = [
+    _K1_INST % ("false, false, false, demi::K1_PLAIN", "K1Args"),          # 0
+    '#include "k2_replay.hpp"',                                             # 1  k2_replay
+    '#include "k3_dpor.hpp"',                                               # 2
+    _K1_INST % ("false, true, false, demi::K1_PLAIN", "K1Args"),           # 3
+    '#include "k2_replay.hpp"',                                             # 4  k2_replay_fp
+    '#include "k2_replay.hpp"',                                             # 5  k2_replay_fp_hbm
+    _K1_INST % ("true, false, false, demi::K1_PLAIN", "K1Args"),           # 6  (6 .. 11: tables without an interpreter only)
+    _K1_INST % ("true, true, false, demi::K1_PLAIN", "K1Args"),            # 7
+    _K1_INST % ("false, false, true, demi::K1_PLAIN", "K1Args"),           # 8
+    _K1_INST % ("false, true, true, demi::K1_PLAIN", "K1Args"),            # 9
+    _K1_INST % ("true, false, true, demi::K1_PLAIN", "K1Args"),            # 10
+    _K1_INST % ("true, true, true, demi::K1_PLAIN", "K1Args"),             # 11
+    '#include "k2_replay.hpp"',                                             # 12 k2_replay_fp_wave
+    _K1_INST % ("false, false, false, demi::K1_REBIN", "K1Args"),          # 13
+    _K1_INST % ("false, false, false, demi::K1_MULTI", "K1MultiArgs"),     # 14
+    _K1_INST % ("false, true, false, demi::K1_MULTI", "K1MultiArgs"),      # 15
+    _K1_INST % ("false, false, false, demi::K1_SPREAD", "K1SpreadArgs"),   # 16
+    _K1_INST % ("false, true, false, demi::K1_SPREAD", "K1SpreadArgs"),    # 17
+    '#include "k2_wildcard.hpp"',                                           # 18
+    '#include "k2_wildcard_cand.hpp"',                                      # 19
+    _K1_INST % ("false, false, false, demi::K1_TESTS", "K1TestsArgs"),     # 20
+    _K1_INST % ("false, true, false, demi::K1_TESTS", "K1TestsArgs"),      # 21
+]
+
+
+def test_module_numbers_name_the_kernels_they_always_named(tmp_path):
+    """Every module number keeps its kernel: the narrow raft (with the workgroup-per-test modules) and the wide one between them
+    get all 22 compiled, and each dumped translation unit ends in the line JIT_MODULES lists for its number."""
+    code = ("import sys, os; sys.path.insert(0, %r)\n"
+            "from demi_amd import _native, model as M\n"
+            "try:\n"
+            "    for name, m in (('narrow', M.raft_model(5)), ('wide', M.raft_model(5, term0=1000, loglen0=300))):\n"
+            "        os.environ['DEMI_JIT_DUMP_SRC'] = os.path.join(%r, name)\n"
+            "        print('SIZE', _native.specialize_check(m.to_struct())[0])\n"
+            "except _native.DemiError as e:\n"
+            "    print('ERR', e)\n" % (ROOT, str(tmp_path)))
+    env = dict(os.environ, DEMI_EXPERIMENT="1", DEMI_SPECIALIZE_CHECK_TESTS="1")
+    for k in ("DEMI_SPECIALIZE_CHECK_K1_ONLY", "DEMI_JIT_DUMP"):
+        env.pop(k, None)
+    out = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=900)
+    if "hiprtc not found" in out.stdout:
+        pytest.skip("no hiprtc in this environment")
+    assert out.stdout.count("SIZE") == 2, out.stdout + out.stderr
+    assert len(JIT_MODULES) == 22
+    dumped = {}
+    for name in ("narrow", "wide"):
+        dumped[name] = set()
+        for k, want in enumerate(JIT_MODULES):
+            path = str(tmp_path / name) + ".%d" % k
+            if not os.path.exists(path):
+                continue
+            assert open(path).read().rstrip("\n").rsplit("\n", 1)[-1] == want, (name, k)
+            dumped[name].add(k)
+        assert not os.path.exists(str(tmp_path / name) + ".22")
+    assert dumped["narrow"] == set(range(22)) - set(range(6, 12))
+    assert dumped["wide"] == set(range(22)) - {4, 5, 12}

@@ -1,5 +1,5 @@
 """GPU suite: RunnerUtils.randomDDMin natively (demi_random_ddmin) and the kernel variant under it (K1 over a frontier of
-candidate subsequences, a workgroup per candidate: k1_random_explore<.., MULTI>, demi_random_explore_candidates).
+candidate subsequences, a workgroup per candidate: k1_random_explore<.., K1_MULTI>, demi_random_explore_candidates).
 
 Held against (a) the CPU oracle one candidate at a time - orc_random_explore on the candidate's own external events, which is
 what `trace_load(candidate)` + demi_random_explore computes - and (b) the reference's loop written out in Python
@@ -37,9 +37,13 @@ def _atom_candidates(events, rng, n_cand):
     return out
 
 
+@pytest.mark.parametrize("lanes", [1, 5, 64])
 @pytest.mark.parametrize("specialize", [False, True])
 @pytest.mark.parametrize("strategy", [T.STRATEGY_FULLY_RANDOM, T.STRATEGY_SRC_DST_FIFO])
-def test_candidate_batch_equals_the_oracle_per_candidate(oracle, specialize, strategy):
+def test_candidate_batch_equals_the_oracle_per_candidate(oracle, monkeypatch, specialize, strategy, lanes):
+    """lanes: DEMI_K1_LANES_PER_WAVE, the executions a wave of the frontier launch runs (unset, the launch picks what fills the chip
+    it runs on) - one, a count that is no power of two and leaves the last workgroup of a candidate partly filled, a full wave."""
+    monkeypatch.setenv("DEMI_K1_LANES_PER_WAVE", str(lanes))
     model, events, lim = raft5_config2()
     lim.strategy = strategy
     R = 70 if not EMU else 40                 # (not a multiple of 64: the last wave of a candidate's workgroup is partly idle)

@@ -7,14 +7,13 @@ compiler (what `python bench.py` uses) and, with --system, with /opt/rocm's (wha
 """
 import argparse
 import os
+import shutil
 import struct
 import subprocess
 import sys
 import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NAMES = ["k1_random_explore<false,false>", "k2_replay (+fp, fp_hbm)", "k3_dpor", "k1_random_explore<false,true> (SrcDstFIFO)",
-         "k2 (same TU)", "k2 (same TU)"]
 
 
 def text_hash(b):
@@ -55,10 +54,10 @@ def main():
     if out.returncode:
         sys.exit(out.stdout + out.stderr)
     objdump, readelf = "/opt/rocm/lib/llvm/bin/llvm-objdump", "/opt/rocm/lib/llvm/bin/llvm-readelf"
-    for k in list(range(6)) + [13]:
+    filt = shutil.which("llvm-cxxfilt") or shutil.which("c++filt")
+    dumped = sorted(int(f.split(".")[-1]) for f in os.listdir(d) if f.startswith("img.") and f.split(".")[-1].isdigit())
+    for k in dumped:            # (the module numbers: demi_gpu.hip JK_*)
         p = os.path.join(d, "img.%d" % k)
-        if not os.path.exists(p) or k in (4, 5):
-            continue
         b = open(p, "rb").read()
         dis = subprocess.run([objdump, "-d", p], capture_output=True, text=True).stdout.splitlines()
         ins = [l.split()[0] for l in dis if l.startswith("\t") and l.split()]
@@ -66,7 +65,11 @@ def main():
         meta = [l.strip() for l in notes.splitlines() if any(x in l for x in (".name:", ".vgpr_count", ".sgpr_count", "spill_count", "private_segment_fixed"))
                 and ".name:           hidden" not in l and "value_kind" not in l]
         comp = [l for l in subprocess.run([readelf, "-p", ".comment", p], capture_output=True, text=True).stdout.splitlines() if "clang version" in l]
-        print("== kernel %d: %s" % (k, NAMES[k] if k < len(NAMES) else "k1_random_explore<false,false,false,true> (re-binned)"))
+        # the label: the kernels the code object holds, as its notes name them
+        syms = [l.split(".name:")[1].strip() for l in meta if l.startswith(".name:")]
+        meta = [l for l in meta if not l.startswith(".name:")]
+        names = subprocess.run([filt], input="\n".join(syms), capture_output=True, text=True).stdout.split("\n") if filt else syms
+        print("== kernel %d: %s" % (k, ", ".join(n.replace("void ", "")[:n.replace("void ", "").find(">(") + 1 or n.replace("void ", "").find("(")] for n in names if n)))
         print("   instructions %d (+ %d s_nop), code id %s, %d bytes" % (sum(1 for i in ins if i != "s_nop"), ins.count("s_nop"), text_hash(b), len(b)))
         print("   " + "  ".join(meta))
         if comp and k == 0:
