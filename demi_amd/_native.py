@@ -21,6 +21,7 @@ EXPORTS = ["demi_ctx_create", "demi_ctx_destroy", "demi_last_error", "demi_versi
            "demi_replay_wildcard_load", "demi_replay_wildcard_batch", "demi_replay_wildcard_get_trace",
            "demi_replay_wildcard_candidates", "demi_wildcard_ddmin",
            "demi_fuzz_stride", "demi_fuzz_generate", "demi_random_explore_tests", "demi_fuzz_campaign",
+           "demi_fuzz_generate_fields", "demi_random_explore_tests_areas", "demi_fuzz_campaign_fields",
            "demi_replay_removal_round", "demi_minimize_internals"]
 
 _lib = None
@@ -150,6 +151,12 @@ def lib():
                                             C.c_void_p, C.c_void_p]
     L.demi_fuzz_campaign.argtypes = [C.c_void_p, C.POINTER(T.FuzzParams), C.POINTER(T.FuzzCampaignParams), C.POINTER(T.Limits), C.c_void_p,
                                      C.c_uint32, C.POINTER(T.FuzzCampaignResult)]
+    L.demi_fuzz_generate_fields.argtypes = [C.c_void_p, C.POINTER(T.FuzzParams), C.POINTER(T.FuzzFieldGen), C.c_uint64, C.c_void_p, C.c_uint32,
+                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.demi_random_explore_tests_areas.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32,
+                                                  C.POINTER(T.Limits), C.c_void_p, C.c_void_p]
+    L.demi_fuzz_campaign_fields.argtypes = [C.c_void_p, C.POINTER(T.FuzzParams), C.POINTER(T.FuzzFieldGen), C.POINTER(T.FuzzCampaignParams),
+                                            C.POINTER(T.Limits), C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(T.FuzzCampaignResult)]
     L.demi_replay_removal_round.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(T.Limits), C.c_void_p,
                                             C.POINTER(T.RemovalRoundResult)]
     L.demi_minimize_internals.argtypes = [C.c_void_p, C.POINTER(T.Limits), C.POINTER(T.IntminParams), C.c_void_p, C.c_uint32,
@@ -364,7 +371,8 @@ class Context:
     @staticmethod
     def fuzz_params(num_events, weights, send_gen, prefix, postfix=()):
         """demi_fuzz_params for Fuzzer(num_events, weights, send_gen, prefix, postfix): (struct, the arrays it points into - keep
-        them alive as long as the struct).  send_gen: fuzzer.SendGenerator; prefix / postfix: event tuples or EXT_EVENT_DTYPE."""
+        them alive as long as the struct).  send_gen: fuzzer.SendGenerator (a FieldSendGenerator travels beside the struct, as
+        field_gen_struct makes it: `gen` stays zero); prefix / postfix: event tuples or EXT_EVENT_DTYPE."""
         import numpy as np
         from . import fuzzer as F
 
@@ -381,14 +389,25 @@ class Context:
         par.total_mass = total
         for i in range(4):
             par.cum[i] = cum[i]
-        C.memmove(C.byref(par.gen), send_gen.to_struct().ctypes.data, C.sizeof(T.FuzzSendGen))
+        if not isinstance(send_gen, F.FieldSendGenerator):
+            C.memmove(C.byref(par.gen), send_gen.to_struct().ctypes.data, C.sizeof(T.FuzzSendGen))
         return par, (pre, post)
+
+    @staticmethod
+    def field_gen_struct(field_gen):
+        """demi_fuzz_field_gen of a fuzzer.FieldSendGenerator"""
+        fg = T.FuzzFieldGen()
+        C.memmove(C.byref(fg), field_gen.to_struct().ctypes.data, C.sizeof(T.FuzzFieldGen))
+        return fg
 
     def fuzz_generate(self, n_tests, num_events, weights, send_gen, prefix, postfix=(), seed_base=0, seeds=None, copy_out=True):
         """demi_fuzz_generate: n_tests tests of Fuzzer(num_events, weights, send_gen, prefix, postfix), test i under
         java.util.Random(seed_base + i) or seeds[i]; they stay resident for random_explore_tests(None, ..).  Returns
-        (events [n_tests, stride], n_ev [n_tests], n_batches [n_tests]); copy_out=False leaves the events on the device (None)."""
+        (events [n_tests, stride], n_ev [n_tests], n_batches [n_tests]); copy_out=False leaves the events on the device (None).
+        With a fuzzer.FieldSendGenerator (demi_fuzz_generate_fields) the payload areas [n_tests, stride] come beside the events:
+        (events, areas, n_ev, n_batches), and stay resident with them."""
         import numpy as np
+        from . import fuzzer as F
         par, keep = self.fuzz_params(num_events, weights, send_gen, prefix, postfix)
         stride = int(lib().demi_fuzz_stride(C.byref(par)))
         ev = np.zeros((n_tests, stride), dtype=T.EXT_EVENT_DTYPE) if copy_out and stride <= T.MAX_EXT_EVENTS else None     # (a longer stride is refused by the call)
@@ -399,17 +418,31 @@ class Context:
             seeds = np.ascontiguousarray(seeds, dtype=np.uint64)
             assert len(seeds) == n_tests
             sp = seeds.ctypes.data
+        if isinstance(send_gen, F.FieldSendGenerator):
+            fg = self.field_gen_struct(send_gen)
+            ar = np.zeros((n_tests, stride), dtype=np.uint64) if ev is not None else None
+            self._check(lib().demi_fuzz_generate_fields(self._h, C.byref(par), C.byref(fg), C.c_uint64(seed_base), sp, n_tests,
+                                                        ev.ctypes.data if ev is not None and n_tests else None,
+                                                        ar.ctypes.data if ar is not None and n_tests else None, n_ev.ctypes.data, n_b.ctypes.data))
+            del keep
+            return ev, ar, n_ev, n_b
         self._check(lib().demi_fuzz_generate(self._h, C.byref(par), C.c_uint64(seed_base), sp, n_tests,
                                              ev.ctypes.data if ev is not None and n_tests else None, n_ev.ctypes.data, n_b.ctypes.data))
         del keep
         return ev, n_ev, n_b
 
-    def random_explore_tests(self, tests, executions, limits, seed_base=0, n_ev=None, n_tests=None):
+    def random_explore_tests(self, tests, executions, limits, seed_base=0, n_ev=None, n_tests=None, areas=None, with_areas=None):
         """K1 with a workgroup per test: (verdicts [n_tests, executions], flags [n_tests]).  tests: [n_tests, stride] events with
-        their lengths n_ev (a list of event arrays is packed), or None for the first n_tests tests fuzz_generate left resident."""
+        their lengths n_ev (a list of event arrays is packed), or None for the first n_tests tests fuzz_generate left resident.
+        areas: the tests' payload areas, shaped like `tests` (a list of per-test arrays is packed with them) - the call then goes
+        through demi_random_explore_tests_areas, which takes a DEMI_MODEL_PAYLOADS table; with_areas=True asks for that entry point
+        without areas (host tests: the areas are made of P0 / P1; None: the resident tests' own)."""
         import numpy as np
+        if with_areas is None:
+            with_areas = areas is not None
+        ap = None
         if tests is None:
-            assert n_tests is not None
+            assert n_tests is not None and areas is None
             tp, np_, stride = None, None, 0
         else:
             if not isinstance(tests, np.ndarray):
@@ -417,6 +450,13 @@ class Context:
                 packed = np.zeros((len(tests), max(lens + [1])), dtype=T.EXT_EVENT_DTYPE)
                 for i, t in enumerate(tests):
                     packed[i, :lens[i]] = np.asarray(t, dtype=T.EXT_EVENT_DTYPE)
+                if areas is not None:
+                    pa = np.zeros(packed.shape, dtype=np.uint64)
+                    for i, a in enumerate(areas):
+                        if len(a) != lens[i]:
+                            raise ValueError("random_explore_tests: test %d has %d events and %d areas" % (i, lens[i], len(a)))
+                        pa[i, :lens[i]] = np.asarray(a, dtype=np.uint64)
+                    areas = pa
                 tests, n_ev = packed, lens
             if n_ev is None:
                 raise ValueError("random_explore_tests: an array of tests needs n_ev, the length of every test")
@@ -426,22 +466,40 @@ class Context:
                 raise ValueError("random_explore_tests: tests is [n_tests, stride] and n_ev [n_tests]")
             n_tests, stride = tests.shape
             tp, np_ = tests.ctypes.data, n_ev.ctypes.data
+            if areas is not None:
+                areas = np.ascontiguousarray(areas, dtype=np.uint64)
+                if areas.shape != tests.shape:
+                    raise ValueError("random_explore_tests: areas is [n_tests, stride] like tests")
+                ap = areas.ctypes.data
         v = np.zeros((n_tests, executions), dtype=T.VERDICT_DTYPE)
         f = np.zeros(n_tests, dtype=np.uint32)
+        if with_areas:
+            self._check(lib().demi_random_explore_tests_areas(self._h, C.c_uint64(seed_base), tp, ap, np_, stride, n_tests, executions,
+                                                              C.byref(limits), v.ctypes.data, f.ctypes.data))
+            return v, f
         self._check(lib().demi_random_explore_tests(self._h, C.c_uint64(seed_base), tp, np_, stride, n_tests, executions, C.byref(limits),
                                                     v.ctypes.data, f.ctypes.data))
         return v, f
 
     def fuzz_campaign(self, num_events, weights, send_gen, prefix, limits, postfix=(), executions_per_test=1, tests_per_launch=256,
                       max_tests=1024, test_seed_base=0, exec_seed_base=0):
-        """demi_fuzz_campaign: (result struct, the violating test's events or None)."""
+        """demi_fuzz_campaign: (result struct, the violating test's events or None).  With a fuzzer.FieldSendGenerator
+        (demi_fuzz_campaign_fields): (result struct, events or None, their payload areas or None)."""
         import numpy as np
+        from . import fuzzer as F
         par, keep = self.fuzz_params(num_events, weights, send_gen, prefix, postfix)
         cp = T.FuzzCampaignParams(test_seed_base=test_seed_base, exec_seed_base=exec_seed_base, executions_per_test=executions_per_test,
                                   tests_per_launch=tests_per_launch, max_tests=max_tests)
         res = T.FuzzCampaignResult()
         cap = T.MAX_EXT_EVENTS
         ev = np.zeros(cap, dtype=T.EXT_EVENT_DTYPE)
+        if isinstance(send_gen, F.FieldSendGenerator):
+            fg = self.field_gen_struct(send_gen)
+            ar = np.zeros(cap, dtype=np.uint64)
+            self._check(lib().demi_fuzz_campaign_fields(self._h, C.byref(par), C.byref(fg), C.byref(cp), C.byref(limits), ev.ctypes.data,
+                                                        ar.ctypes.data, cap, C.byref(res)))
+            del keep
+            return (res, ev[:res.n_events].copy(), ar[:res.n_events].copy()) if res.found else (res, None, None)
         self._check(lib().demi_fuzz_campaign(self._h, C.byref(par), C.byref(cp), C.byref(limits), ev.ctypes.data, cap, C.byref(res)))
         del keep
         return res, (ev[:res.n_events].copy() if res.found else None)

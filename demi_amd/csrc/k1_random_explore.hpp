@@ -76,6 +76,7 @@ struct K1TestsArgs : K1Args {
   uint32_t populate_all;        // 1 = `exists` as given; 0 = the actors the TEST Start()s (what trace_load derives)
   uint32_t* test_flags;         // [n_tests], zeroed by the host: bit 0 = some execution violated, bit 1 = some execution aborted on a capacity
   uint32_t lanes_per_wave;      // 0 = 64; as in K1MultiArgs
+  const uint64_t* test_areas;   // [n_tests][stride] a DEMI_MODEL_PAYLOADS table's payload area of every Send (read by its compiled kernel only)
 };
 // The four front ends exclude each other, so they are one template parameter: a kernel is <REC, FIFO, CARRY, variant>.
 enum K1Variant { K1_PLAIN, K1_REBIN, K1_MULTI, K1_SPREAD, K1_TESTS };
@@ -332,10 +333,19 @@ __global__ K1_LAUNCH_BOUNDS void k1_random_explore(const typename K1ArgsOf<V>::t
 #ifdef DEMI_JIT_NPAY
       // (a table whose messages have more than two fields: the Send's whole payload area, staged by demi_ext_payload_areas or
       // made of P0 / P1 by the load - behind the events in the same array)
+      // (TESTS: the area comes from the test's own row of test_areas, [n_tests][stride] like the events.  Thread 0 reads each area
+      // once, here: straight from global memory, nothing of it in LDS.  The other front ends keep their statement as it was.)
       const uint32_t orig = MULTI ? (uint32_t)s_sendw[i] : i;
-      const word_t sw = (kind == DEMI_EV_SEND && ((t.exists >> a) & 1))
-                            ? msg_word_area((uint32_t)(ev >> 24) & 0xFF, DL, a, args.trace[EXT_AREA_OFFSET + orig] & 0xFFFFFFFFFFFFull)
-                            : (word_t)0;
+      word_t sw;
+      if constexpr (TESTS) {
+        sw = (kind == DEMI_EV_SEND && ((t.exists >> a) & 1))
+                 ? msg_word_area((uint32_t)(ev >> 24) & 0xFF, DL, a, args.test_areas[(size_t)m_cand * args.stride + i] & 0xFFFFFFFFFFFFull)
+                 : (word_t)0;
+      } else {
+        sw = (kind == DEMI_EV_SEND && ((t.exists >> a) & 1))
+                 ? msg_word_area((uint32_t)(ev >> 24) & 0xFF, DL, a, args.trace[EXT_AREA_OFFSET + orig] & 0xFFFFFFFFFFFFull)
+                 : (word_t)0;
+      }
       (void)ep0; (void)ep1;
 #else
       const word_t sw = (kind == DEMI_EV_SEND && ((t.exists >> a) & 1))

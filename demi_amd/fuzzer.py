@@ -300,6 +300,104 @@ class SendGenerator:
         return s
 
 
+# The same for messages with more than two fields (include/demi_gpu.h demi_fuzz_field_gen, k_fuzz_generate_fields): an alternative
+# is (msg_type, target, [field, ..]) with up to six fields.  The draw order: the alternative with next_int(n) only when n > 1, the
+# target, then the fields 0, 1, .. in that order - with two fields each, SendGenerator's.  The field width is the table's.
+MAX_PAYLOADS = 6
+FIELD_ALT_DTYPE = np.dtype([("msg_type", "u1"), ("target_kind", "u1"), ("target_actor", "u1"), ("n_fields", "u1"),
+                            ("kind", "u1", (MAX_PAYLOADS,)), ("pad", "u1", (2,)), ("arg", "<u4", (MAX_PAYLOADS,))])     # demi_fuzz_field_alt
+FIELD_GEN_DTYPE = np.dtype([("n_alts", "<u4"), ("pad", "<u4"), ("alts", FIELD_ALT_DTYPE, (FUZZ_MAX_ALTS,))])          # demi_fuzz_field_gen
+
+
+def model_field_layout(model):
+    """(fields per message, field width W) of a table, as the library derives them: 2 fields of 8 bits for a narrow table, of 16
+    for a wide one; DEMI_MODEL_PAYLOADS(n): n fields of DEMI_PAYLOAD_BITS(n) = 16, 12, 9, 8 bits."""
+    npay = int(getattr(model, "payloads", 0) or 0)
+    if npay > 2:
+        return npay, T.payload_bits(npay)
+    return 2, 16 if getattr(model, "wide", False) else 8
+
+
+class FieldSendGenerator:
+    """alternatives: [(msg_type, target, [field, ..])] with target RANDOM_ALIVE / FIXED(actor) and up to as many fields as a
+    message of `model` has, each CONST(v) / COUNTER / RANDOM(bound); the fields an alternative leaves out are 0.  COUNTER = the
+    Sends generated so far in this test, starting at 1, masked to the field width.  Callable as generate_fuzz_test's
+    message_gen: the Send it returns carries P0 / P1 = fields 0 / 1, and `sent` remembers every generated Send's field list
+    (one list per Send of the current test, in order) - generate_fuzz_test_fields makes the payload areas of them."""
+
+    def __init__(self, alternatives, model):
+        self.n_payloads, self.field_bits = model_field_layout(model)
+        self.with_areas = int(getattr(model, "payloads", 0) or 0) > 2
+        alternatives = [(a[0], tuple(a[1]), [tuple(f) for f in a[2]]) for a in alternatives]
+        if not 1 <= len(alternatives) <= FUZZ_MAX_ALTS:
+            raise ValueError("a FieldSendGenerator holds 1..%d alternatives" % FUZZ_MAX_ALTS)
+        lim = 1 << self.field_bits
+        for msg_type, target, fields in alternatives:
+            if not 0 <= msg_type < 32:
+                raise ValueError("message type %r" % (msg_type,))
+            if target[0] not in (TARGET_RANDOM_ALIVE, TARGET_FIXED) or not 0 <= target[1] < 16:
+                raise ValueError("target %r" % (target,))
+            if len(fields) > self.n_payloads:
+                raise ValueError("%d fields described, a message of the table has %d" % (len(fields), self.n_payloads))
+            for kind, arg in fields:
+                if kind not in (FIELD_CONST, FIELD_COUNTER, FIELD_RANDOM):
+                    raise ValueError("unknown field kind %r" % ((kind, arg),))
+                if kind == FIELD_CONST and not 0 <= arg < lim:
+                    raise ValueError("CONST(%d) does not fit %d bits" % (arg, self.field_bits))
+                if kind == FIELD_RANDOM and not 1 <= arg <= min(lim, 256):
+                    raise ValueError("RANDOM(%d): the bound is 1..%d" % (arg, min(lim, 256)))
+        self.alternatives = alternatives
+        self._rng, self.counter, self.sent, self._sent_events = None, 0, [], []
+
+    def __call__(self, rng, alive):
+        if rng is not self._rng:
+            self._rng, self.counter, self.sent, self._sent_events = rng, 0, [], []
+        self.counter += 1
+        alts = self.alternatives
+        msg_type, target, fields = alts[rng.next_int(len(alts))] if len(alts) > 1 else alts[0]
+        if target[0] == TARGET_RANDOM_ALIVE:
+            a = alive.get_random() if len(alive) else 0
+        else:
+            a = target[1]
+        mask = (1 << self.field_bits) - 1
+        vals = []
+        for kind, arg in fields:
+            vals.append(arg if kind == FIELD_CONST else self.counter & mask if kind == FIELD_COUNTER else rng.next_int(arg))
+        ev = send(a, msg_type, vals[0] if len(vals) > 0 else 0, vals[1] if len(vals) > 1 else 0)
+        self.sent.append(vals)
+        self._sent_events.append(ev)
+        return ev
+
+    def area(self, vals) -> int:
+        """the payload area of a Send with these fields: 0 for a table without DEMI_MODEL_PAYLOADS"""
+        return T.pay_area(vals, self.n_payloads) if self.with_areas else 0
+
+    def to_struct(self) -> np.ndarray:
+        s = np.zeros(1, dtype=FIELD_GEN_DTYPE)
+        s["n_alts"] = len(self.alternatives)
+        for i, (msg_type, target, fields) in enumerate(self.alternatives):
+            a = s["alts"][0][i]
+            a["msg_type"], a["target_kind"], a["target_actor"], a["n_fields"] = msg_type, target[0], target[1], len(fields)
+            for k, (kind, arg) in enumerate(fields):
+                a["kind"][k], a["arg"][k] = kind, arg
+        return s
+
+
+def generate_fuzz_test_fields(num_events: int, weights: FuzzerWeights, field_gen: FieldSendGenerator, prefix: List[Event],
+                              seed: int, postfix: List[Event] = ()):
+    """generate_fuzz_test with a FieldSendGenerator: (events, areas), areas[i] the 48-bit payload area of event i - of a
+    generated Send its fields packed by T.pay_area, of a Send of the prefix / postfix what trace_load makes of P0 / P1 with
+    nothing staged, 0 for every other event and for a table without DEMI_MODEL_PAYLOADS.  The mirror of
+    k_fuzz_generate_fields, byte for byte."""
+    field_gen._rng = None                       # (this test's count starts at 1, whatever the generator object generated before)
+    field_gen.sent, field_gen._sent_events = [], []
+    events = generate_fuzz_test(num_events, weights, field_gen, prefix, seed, postfix)
+    # (a generated Send is the very tuple the generator returned; a Send of the prefix / postfix is not)
+    made = {id(e): vals for e, vals in zip(field_gen._sent_events, field_gen.sent)}
+    areas = [0 if e[0] != T.EV_SEND else field_gen.area(made[id(e)] if id(e) in made else [e[4], e[5]]) for e in events]
+    return events, areas
+
+
 def raft_send_generator() -> SendGenerator:
     """raft_trace's closure as a descriptor: ClientRequest(counter) to a random live node."""
     from .model import M_CLIENT

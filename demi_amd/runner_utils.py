@@ -27,7 +27,8 @@ def fuzz(generateFuzzTest: Callable[[int], np.ndarray], schedulerConfig: Schedul
     The reference runs ONE random execution per generated test (`new RandomScheduler(config, 1, interval, strategy)`);
     a launch evaluates `executions_per_test` seeded interleavings of the same test and explore() reports the first
     violating one.  generateFuzzTest(i) is Fuzzer.generateFuzzTest for the i-th attempt (fuzzer.generate_fuzz_test /
-    raft_trace with a seed derived from i).  Returns (trace, violation, initialTrace, filtered) — the depGraph of the
+    raft_trace with a seed derived from i); it may return (events, areas) - fuzzer.generate_fuzz_test_fields: the external
+    Sends of a DEMI_MODEL_PAYLOADS table with all their fields -, and the execution is then loaded with those areas.  Returns (trace, violation, initialTrace, filtered) — the depGraph of the
     reference is implicit in the causal-path keys of initialTrace — or None after max_tests tests without a violation
     (the reference loops forever).  provenance_device: the GPU ProvenanceTracker runs on (demi_provenance_prune); -1 = device
     0 when the executions ran on the GPU scheduler (the default scheduler_ctor), the host class (demi_amd/provenance.py)
@@ -35,13 +36,16 @@ def fuzz(generateFuzzTest: Callable[[int], np.ndarray], schedulerConfig: Schedul
     if provenance_device == -1:
         provenance_device = 0 if scheduler_ctor is RandomScheduler else None
     for attempt in range(max_tests):
-        fuzzTest = np.ascontiguousarray(generateFuzzTest(attempt), dtype=T.EXT_EVENT_DTYPE)
+        fuzzTest, areas = generateFuzzTest(attempt), None
+        if isinstance(fuzzTest, tuple) and len(fuzzTest) == 2:
+            fuzzTest, areas = fuzzTest
+        fuzzTest = np.ascontiguousarray(fuzzTest, dtype=T.EXT_EVENT_DTYPE)
         sched = scheduler_ctor(schedulerConfig, executions_per_test, invariant_check_interval,
                                randomizationStrategy=randomizationStrategyCtor())
         if maxMessages is not None:
             sched.setMaxMessages(maxMessages)
         try:
-            found = sched.explore(fuzzTest)
+            found = sched.explore(fuzzTest) if areas is None else sched.explore(fuzzTest, areas=areas)
         finally:
             sched.shutdown()
         if found is None:
@@ -83,14 +87,18 @@ def fuzz_campaign(fuzzer_args, schedulerConfig: SchedulerConfig,
                   maxMessages: Optional[int] = None, randomizationStrategyCtor: Callable[[], object] = FullyRandom,
                   computeProvenance: bool = True, violationWereLookingFor: Callable[[ViolationFingerprint], bool] = lambda f: True,
                   executions_per_test: int = 64, max_tests: int = 1024, tests_per_launch: int = 256, test_seed_base: int = 0,
-                  provenance_device: Optional[int] = 0, device: int = 0, p_max: int = 64, specialize: bool = False
+                  provenance_device: Optional[int] = 0, device: int = 0, p_max: int = 64, specialize: bool = False, ctx=None
                   ) -> Optional[Tuple[EventTrace, ViolationFingerprint, np.ndarray, np.ndarray]]:
     """fuzz() with the test axis on the device: what fuzz(lambda i: generate_fuzz_test(.., seed = test_seed_base + i), ..) returns
     for the same executions_per_test and max_tests - (trace, violation, initialTrace, filtered) or None - found by launches of
     tests_per_launch generated tests each (demi_fuzz_campaign: k_fuzz_generate, K1 with a workgroup per test, the per-test flags).
 
     fuzzer_args: (num_events, weights, send_generator, prefix[, postfix]) - Fuzzer's constructor arguments with the
-    MessageGenerator as a fuzzer.SendGenerator.  The one (test, execution) the device reports is re-run through the recording
+    MessageGenerator as a fuzzer.SendGenerator, or as a fuzzer.FieldSendGenerator: generated Sends with up to six fields
+    (demi_fuzz_campaign_fields), which is how a DEMI_MODEL_PAYLOADS table is fuzzed; the found execution is then recorded with
+    the test's payload areas and the EventTrace carries them (ext_areas).
+    ctx: a caller's _native.Context with the model loaded (and specialised, where the table needs it): it is used and NOT
+    closed, so that many campaigns share one compilation of the table; `device` and `specialize` are then the caller's.  The one (test, execution) the device reports is re-run through the recording
     path (RandomScheduler.explore's own last step) for its EventTrace; replay validation, violationWereLookingFor and the
     provenance pruning are fuzz()'s, and a test they reject sends the campaign on from the test after it.  When an execution
     before the reported one was aborted on a capacity, the campaign goes on with the largest pending set (fuzz() decides such an
@@ -107,17 +115,23 @@ def fuzz_campaign(fuzzer_args, schedulerConfig: SchedulerConfig,
     mm = 0 if maxMessages is None or maxMessages >= 0x7FFFFFFF else maxMessages
     lim = T.Limits(mm, max(0, invariant_check_interval), p_max, 0, 0, 1 if schedulerConfig.populate_all_actors else 0,
                    T.STRATEGY_SRC_DST_FIFO if isinstance(strategy, SrcDstFIFO) else T.STRATEGY_FULLY_RANDOM)
-    ctx = _native.Context(device)
+    from .fuzzer import FieldSendGenerator
+    with_fields = isinstance(send_gen, FieldSendGenerator)
+    own_ctx = ctx is None
+    if own_ctx:
+        ctx = _native.Context(device)
     try:
-        ctx.model_load(model.to_struct())
-        if getattr(model, "compiled_only", False) or specialize:
-            ctx.model_specialize()
+        if own_ctx:
+            ctx.model_load(model.to_struct())
+            if getattr(model, "compiled_only", False) or specialize:
+                ctx.model_specialize()
         start = 0
         while start < max_tests:
-            res, fuzzTest = ctx.fuzz_campaign(num_events, weights, send_gen, prefix, lim, postfix=postfix,
-                                              executions_per_test=executions_per_test, tests_per_launch=tests_per_launch,
-                                              max_tests=max_tests - start, test_seed_base=test_seed_base + start,
-                                              exec_seed_base=exec_seed_base)
+            res, fuzzTest, *found_areas = ctx.fuzz_campaign(num_events, weights, send_gen, prefix, lim, postfix=postfix,
+                                                            executions_per_test=executions_per_test, tests_per_launch=tests_per_launch,
+                                                            max_tests=max_tests - start, test_seed_base=test_seed_base + start,
+                                                            exec_seed_base=exec_seed_base)
+            areas = found_areas[0] if with_fields else None
             if res.capacity_aborts:
                 # an execution aborted on a capacity has no verdict.  fuzz() decides it alone with the largest pending set; a verdict
                 # does not depend on p_max unless the execution overflows, so the campaign from this test on with the largest
@@ -129,10 +143,11 @@ def fuzz_campaign(fuzzer_args, schedulerConfig: SchedulerConfig,
             if not res.found:
                 return None
             start += int(res.test_index) + 1
-            ctx.trace_load(fuzzTest)
+            ctx.trace_load(fuzzTest, areas)
             v, rec = ctx.random_get_trace(exec_seed_base + int(res.exec_index), lim)
             assert v.flags & T.V_VIOLATION and int(v.fingerprint) == int(res.verdict.fingerprint)
-            trace = EventTrace(rec, fuzzTest[:T.verdict_trace_idx(v.flags)])
+            used = T.verdict_trace_idx(v.flags)
+            trace = EventTrace(rec, fuzzTest[:used], None if areas is None else areas[:used].copy())
             violation = ViolationFingerprint(int(v.fingerprint), model.fp_match_mask)
             if not violationWereLookingFor(violation):
                 continue
@@ -159,7 +174,8 @@ def fuzz_campaign(fuzzer_args, schedulerConfig: SchedulerConfig,
             return trace, violation, initialTrace, filtered
         return None
     finally:
-        ctx.close()
+        if own_ctx:
+            ctx.close()
 
 
 def _prune_on(device, initialTrace, violation):

@@ -56,6 +56,7 @@ class EventTrace:
     """EventTrace.scala:20: the recorded events of one execution + the externals that drove it."""
     events: np.ndarray                 # REC_EVENT_DTYPE
     original_externals: np.ndarray     # EXT_EVENT_DTYPE
+    ext_areas: Optional[np.ndarray] = None   # uint64 per external: the payload areas the execution was loaded with (DEMI_MODEL_PAYLOADS), if any
 
 
 class MinimizationStats:
@@ -137,7 +138,7 @@ class RandomScheduler:
                         1 if self.schedulerConfig.populate_all_actors else 0, self.strategy, 0,
                         self.max_executions if self.carried_generator and self.max_executions > 1 else 0)
 
-    def _prepare(self, trace):
+    def _prepare(self, trace, areas=None):
         if self._model is None or self._model.inv_kind == T.INV_NONE:
             # IllegalArgumentException("Must invoke setInvariant before test()") (:244-246)
             raise ValueError("Must invoke setInvariant before test()")
@@ -154,8 +155,11 @@ class RandomScheduler:
                     pass                     # no run-time compiler here: the table interpreter is used
         ev = np.ascontiguousarray(trace, dtype=T.EXT_EVENT_DTYPE)
         key = ev.tobytes()
+        if areas is not None:
+            areas = np.ascontiguousarray(areas, dtype=np.uint64)
+            key = (key, areas.tobytes())
         if self._loaded_trace != key:
-            self._ctx.trace_load(ev)
+            self._ctx.trace_load(ev, areas)
             self._loaded_trace = key
         return ev
 
@@ -168,11 +172,14 @@ class RandomScheduler:
         self.last_aborted = int(((v["flags"] & OVF_FLAGS) != 0).sum())      # verdicts without a valid answer (capacity)
         return v
 
-    def explore(self, _trace, _lookingFor: Optional[ViolationFingerprint] = None
+    def explore(self, _trace, _lookingFor: Optional[ViolationFingerprint] = None, areas=None
                 ) -> Optional[Tuple[EventTrace, ViolationFingerprint]]:
         """explore (:234-272): the first violating execution, or None.  The GPU evaluates all
-        max_executions schedules; the reference-compatible answer is the lowest index."""
-        ev = self._prepare(_trace)
+        max_executions schedules; the reference-compatible answer is the lowest index.
+        areas: the payload areas of the external Sends of a DEMI_MODEL_PAYLOADS table (Context.ext_payload_areas), one per
+        event of _trace; the returned EventTrace carries the ones of the externals it kept (ext_areas)."""
+        ev = self._prepare(_trace, areas)
+        kept_areas = (lambda n: None) if areas is None else (lambda n: np.ascontiguousarray(areas, dtype=np.uint64)[:n].copy())
         if self.stats is not None:
             self.stats.increment_replays(self.max_executions)
         if self.carried_generator and self.max_executions > 1:
@@ -189,7 +196,7 @@ class RandomScheduler:
             assert ran == i and v1.flags & T.V_VIOLATION
             used = ev[:T.verdict_trace_idx(v1.flags)]
             mask = self._model.fp_match_mask if self._model else 0xFFFFFFFF
-            return EventTrace(rec, used), ViolationFingerprint(int(v1.fingerprint), mask)
+            return EventTrace(rec, used, kept_areas(len(used))), ViolationFingerprint(int(v1.fingerprint), mask)
         # only the violating and the aborted executions cross PCIe (16 B each instead of 16 B per schedule).  An execution
         # aborted on a capacity has no valid verdict: it is re-run alone with the largest pending set before any
         # higher index is believed (the reference has no capacities; its answer is the lowest violating index)
@@ -254,7 +261,7 @@ class RandomScheduler:
         # checkIfBugFound prunes the externals that were never injected (:160-163)
         used = ev[:T.verdict_trace_idx(v.flags)]
         mask = self._model.fp_match_mask if self._model else 0xFFFFFFFF
-        return EventTrace(rec, used), ViolationFingerprint(int(v.fingerprint), mask)
+        return EventTrace(rec, used, kept_areas(len(used))), ViolationFingerprint(int(v.fingerprint), mask)
 
     def _explore_one_call(self, ev, _lookingFor):
         """explore() as rounds 1-5 ran it: ONE device call for all the executions (kept for the comparison in the suite)."""

@@ -182,6 +182,17 @@ class FuzzParams(C.Structure):
                 ("gen", FuzzSendGen)]
 
 
+class FuzzFieldAlt(C.Structure):
+    """demi_fuzz_field_alt"""
+    _fields_ = [("msg_type", C.c_uint8), ("target_kind", C.c_uint8), ("target_actor", C.c_uint8), ("n_fields", C.c_uint8),
+                ("kind", C.c_uint8 * 6), ("pad", C.c_uint8 * 2), ("arg", C.c_uint32 * 6)]
+
+
+class FuzzFieldGen(C.Structure):
+    """demi_fuzz_field_gen"""
+    _fields_ = [("n_alts", C.c_uint32), ("pad", C.c_uint32), ("alts", FuzzFieldAlt * 8)]
+
+
 class FuzzCampaignParams(C.Structure):
     """demi_fuzz_campaign_params"""
     _fields_ = [("test_seed_base", C.c_uint64), ("exec_seed_base", C.c_uint64), ("executions_per_test", C.c_uint32),

@@ -1075,7 +1075,8 @@ int demi_fuzz_generate(demi_ctx* ctx, const demi_fuzz_params* params, uint64_t s
  * stride ignored) for the tests the last demi_fuzz_generate left in the context (n_tests <= what it generated).  out_flags
  * [n_tests]: bit 0 = some execution of the test violated (limits.looking_for applies), bit 1 = some execution was aborted on a
  * capacity.  Either output may be NULL.  The loaded trace, if any, is neither used nor changed.  DEMI_ERR_INVALID_ARG for a
- * DEMI_MODEL_PAYLOADS table (a generated Send has two fields; per-test payload areas are not built). */
+ * DEMI_MODEL_PAYLOADS table: this entry point cannot say what fields 2..5 of a Send are (demi_random_explore_tests_areas below
+ * takes every table; demi_fuzz_campaign refuses such a table for the same reason, demi_fuzz_campaign_fields takes it). */
 int demi_random_explore_tests(demi_ctx* ctx, uint64_t seed_base, const demi_ext_event* tests, const uint32_t* n_ev, uint32_t stride,
                               uint32_t n_tests, uint32_t executions, const demi_limits* limits, demi_verdict* out_verdicts,
                               uint32_t* out_flags);
@@ -1103,6 +1104,60 @@ typedef struct {
 int demi_fuzz_campaign(demi_ctx* ctx, const demi_fuzz_params* params, const demi_fuzz_campaign_params* campaign,
                        const demi_limits* limits, demi_ext_event* out_events /* [cap] */, uint32_t cap,
                        demi_fuzz_campaign_result* result);
+
+/* ---------------------------------------------------------- fuzz campaigns for messages with more than two fields
+ * The three entry points above describe a Send by P0 and P1.  A DEMI_MODEL_PAYLOADS table's external Send has up to
+ * DEMI_MAX_PAYLOADS fields (demi_ext_payload_areas), so its generator describes up to six: 1..DEMI_FUZZ_MAX_ALTS alternatives,
+ * each (msg_type, target, n_fields, kind[k] / arg[k] for field k) with the kinds of demi_fuzz_field.  n_fields is
+ * 0..DEMI_MAX_PAYLOADS and at most the loaded table's field count (2 without DEMI_MODEL_PAYLOADS); the fields from n_fields
+ * up are 0.  THE FIELD WIDTH W is the library's, taken from the loaded table: 8 for a narrow table, 16 for a DEMI_MODEL_WIDE
+ * table with up to 3 fields, DEMI_PAYLOAD_BITS(n) beyond (12, 9, 8 for n = 4, 5, 6).  CONST must fit W, COUNTER is masked to W,
+ * RANDOM's bound is 1..min(256, 2^W).
+ * THE DRAW ORDER of one generated Send, which the host mirror (demi_amd/fuzzer.py FieldSendGenerator) and
+ * k_fuzz_generate_fields share:
+ *   1. the alternative: nextInt(n_alts) - only when n_alts > 1;   2. the target (RANDOM_ALIVE with somebody alive: nextInt(|alive|));
+ *   3. the fields 0, 1, .., n_fields - 1 in that order (RANDOM: nextInt(arg[k]); CONST and COUNTER draw nothing).
+ * With two-field alternatives this is the draw sequence of demi_fuzz_send_gen above; the draws of generateFuzzTest around it
+ * are the same.
+ * A GENERATED SEND is a demi_ext_event with P0 / P1 = fields 0 / 1 plus its AREA: the fields packed as DEMI_PAYLOAD_OF reads
+ * them (field k in bits [k * W, (k + 1) * W)), or 0 for a table without DEMI_MODEL_PAYLOADS.  Every other event's area is 0,
+ * except a Send of the prefix or postfix: it gets the area demi_trace_load makes of its P0 / P1 with nothing staged. */
+typedef struct {
+  uint8_t msg_type;
+  uint8_t target_kind;     /* demi_fuzz_target */
+  uint8_t target_actor;    /* DEMI_FUZZ_TARGET_FIXED */
+  uint8_t n_fields;        /* 0..DEMI_MAX_PAYLOADS, at most the table's field count */
+  uint8_t kind[DEMI_MAX_PAYLOADS];   /* demi_fuzz_field of field k; ignored from n_fields up */
+  uint8_t pad[2];
+  uint32_t arg[DEMI_MAX_PAYLOADS];   /* CONST: the value; RANDOM: the bound */
+} demi_fuzz_field_alt;     /* 36 bytes */
+typedef struct {
+  uint32_t n_alts;         /* 1..DEMI_FUZZ_MAX_ALTS */
+  uint32_t pad;
+  demi_fuzz_field_alt alts[DEMI_FUZZ_MAX_ALTS];
+} demi_fuzz_field_gen;     /* 296 bytes */
+/* demi_fuzz_generate with the generator above (params->gen is ignored) and the areas beside the events: out_areas
+ * [n_tests][stride] uint64_t, zero off the Sends and behind a test's length; may be NULL like the other outputs.  Events AND
+ * areas stay resident for demi_random_explore_tests_areas(tests = NULL).  DEMI_ERR_INVALID_ARG by name, beyond what
+ * demi_fuzz_generate refuses: an alternative with more fields than the table has, a CONST that does not fit W, a RANDOM bound
+ * outside 1..min(256, 2^W), an unknown kind. */
+int demi_fuzz_generate_fields(demi_ctx* ctx, const demi_fuzz_params* params, const demi_fuzz_field_gen* field_gen, uint64_t seed_base,
+                              const uint64_t* seeds, uint32_t n_tests, demi_ext_event* out_events, uint64_t* out_areas,
+                              uint32_t* out_n_ev, uint32_t* out_n_batches);
+/* demi_random_explore_tests for ANY table: out_verdicts[i * executions + k] is, byte for byte, what demi_ext_payload_areas(areas
+ * of test i) + demi_trace_load(test i) + demi_random_explore(seed_base + k) returns.  areas [n_tests][stride], read for Send
+ * events only; areas = NULL with host tests: the areas are made of P0 / P1, as a load without staged areas does.  tests = NULL
+ * (areas, n_ev, stride ignored): the events and areas the last demi_fuzz_generate_fields (or the events demi_fuzz_generate)
+ * left in the context.  A table without DEMI_MODEL_PAYLOADS ignores the areas. */
+int demi_random_explore_tests_areas(demi_ctx* ctx, uint64_t seed_base, const demi_ext_event* tests, const uint64_t* areas,
+                                    const uint32_t* n_ev, uint32_t stride, uint32_t n_tests, uint32_t executions,
+                                    const demi_limits* limits, demi_verdict* out_verdicts, uint32_t* out_flags);
+/* demi_fuzz_campaign with the generator above (params->gen is ignored): the same launches, the same result.  The found test's
+ * areas go to out_areas [cap] (may be NULL). */
+int demi_fuzz_campaign_fields(demi_ctx* ctx, const demi_fuzz_params* params, const demi_fuzz_field_gen* field_gen,
+                              const demi_fuzz_campaign_params* campaign, const demi_limits* limits,
+                              demi_ext_event* out_events /* [cap] */, uint64_t* out_areas /* [cap] */, uint32_t cap,
+                              demi_fuzz_campaign_result* result);
 
 /* ---------------------------------------------------------- measurement helpers (no reference counterpart)
  * Used by bench.py and the profiling scripts so that the figures beside the throughput are measured on the box that

@@ -793,11 +793,11 @@ static int fuzzer_of(JNIEnv* e, jint numEvents, jbyteArray prefix, jbyteArray po
   jlong w[5];
   memset(f, 0, sizeof *f);
   if (numEvents < 0 || np < 0 || np % 8 || nq % 8 || np / 8 > DEMI_MAX_EXT_EVENTS || nq / 8 > DEMI_MAX_EXT_EVENTS || LEN(weightBits) != 5 ||
-      LEN(gen) != (int64_t)sizeof(demi_fuzz_send_gen))
+      (gen && LEN(gen) != (int64_t)sizeof(demi_fuzz_send_gen)))      /* (gen = NULL: the *Fields entry points, whose generator travels beside) */
     return DEMI_ERR_INVALID_ARG;
   (*e)->GetByteArrayRegion(e, prefix, 0, (jsize)np, (jbyte*)f->fix);
   if (nq) (*e)->GetByteArrayRegion(e, postfixOrNull, 0, (jsize)nq, (jbyte*)(f->fix + DEMI_MAX_EXT_EVENTS));
-  (*e)->GetByteArrayRegion(e, gen, 0, (jsize)sizeof(demi_fuzz_send_gen), (jbyte*)&f->par.gen);
+  if (gen) (*e)->GetByteArrayRegion(e, gen, 0, (jsize)sizeof(demi_fuzz_send_gen), (jbyte*)&f->par.gen);
   {
     void* wb = LONGS(weightBits);
     if (LOST(weightBits, wb)) return DEMI_ERR_INVALID_ARG;
@@ -888,6 +888,109 @@ JNIEXPORT jint JNICALL FN(fuzzCampaign)(JNIEnv* e, jclass c, jlong h, jint numEv
   void* ev = BYTES(events);
   jint rc = LOST(events, ev) ? DEMI_ERR_INVALID_ARG
             : demi_fuzz_campaign(CTX(h), &f.par, &cp, &lim, (demi_ext_event*)ev, DEMI_MAX_EXT_EVENTS, &res);
+  PUT_BYTES(events, ev, 0);
+  if (rc) return rc;
+  o[0] = (jlong)res.found; o[1] = (jlong)res.test_index; o[2] = (jlong)res.exec_index; o[3] = (jlong)res.n_events; o[4] = (jlong)res.tests_run;
+  o[5] = (jlong)res.launches; o[6] = (jlong)res.capacity_aborts;
+  o[7] = (jlong)((uint64_t)res.verdict.flags | ((uint64_t)res.verdict.fingerprint << 32)); o[8] = (jlong)res.verdict.hash;
+  SET_LONGS(result, 9, o);
+  return rc;
+}
+
+/* ---- the same for messages with more than two fields (demi_fuzz_generate_fields / demi_random_explore_tests_areas /
+ *      demi_fuzz_campaign_fields): fieldGen: byte[296] (demi_fuzz_field_gen); areas: long[] beside every byte[8 * ..] of events */
+static int field_gen_of(JNIEnv* e, jbyteArray fieldGen, demi_fuzz_field_gen* g) {
+  if (!fieldGen || LEN(fieldGen) != (int64_t)sizeof(demi_fuzz_field_gen)) return DEMI_ERR_INVALID_ARG;
+  (*e)->GetByteArrayRegion(e, fieldGen, 0, (jsize)sizeof(demi_fuzz_field_gen), (jbyte*)g);
+  return DEMI_OK;
+}
+
+/* areasOrNull: long[nTests * stride], beside eventsOrNull */
+JNIEXPORT jint JNICALL FN(fuzzGenerateFields)(JNIEnv* e, jclass c, jlong h, jint numEvents, jbyteArray prefix, jbyteArray postfixOrNull,
+                                             jlongArray weightBits, jbyteArray fieldGen, jlong seedBase, jlongArray seedsOrNull, jint nTests,
+                                             jbyteArray eventsOrNull, jlongArray areasOrNull, jintArray nEv, jintArray nBatchesOrNull) {
+  jni_fuzzer f;
+  demi_fuzz_field_gen g;
+  (void)c;
+  if (fuzzer_of(e, numEvents, prefix, postfixOrNull, weightBits, NULL, &f) || field_gen_of(e, fieldGen, &g) || nTests < 0 || !nEv ||
+      LEN(nEv) < nTests || (nBatchesOrNull && LEN(nBatchesOrNull) < nTests) || (seedsOrNull && LEN(seedsOrNull) < nTests) ||
+      (eventsOrNull && LEN(eventsOrNull) < 8 * (int64_t)nTests * (int64_t)demi_fuzz_stride(&f.par)) ||
+      (areasOrNull && LEN(areasOrNull) < (int64_t)nTests * (int64_t)demi_fuzz_stride(&f.par)))
+    return DEMI_ERR_INVALID_ARG;
+  void* sd = LONGS(seedsOrNull);
+  void* ev = BYTES(eventsOrNull);
+  void* ar = LONGS(areasOrNull);
+  void* ne = INTS(nEv);
+  void* nb = INTS(nBatchesOrNull);
+  jint rc = (LOST(seedsOrNull, sd) || LOST(eventsOrNull, ev) || LOST(areasOrNull, ar) || LOST(nEv, ne) || LOST(nBatchesOrNull, nb))
+                ? DEMI_ERR_INVALID_ARG
+                : demi_fuzz_generate_fields(CTX(h), &f.par, &g, (uint64_t)seedBase, (const uint64_t*)sd, (uint32_t)nTests, (demi_ext_event*)ev,
+                                            (uint64_t*)ar, (uint32_t*)ne, (uint32_t*)nb);
+  PUT_INTS(nBatchesOrNull, nb, 0);
+  PUT_INTS(nEv, ne, 0);
+  PUT_LONGS(areasOrNull, ar, 0);
+  PUT_BYTES(eventsOrNull, ev, 0);
+  PUT_LONGS(seedsOrNull, sd, JNI_ABORT);
+  return rc;
+}
+
+/* randomExploreTests for any table: areasOrNull: long[nTests * stride] beside testsOrNull (null with tests: the areas are made of
+ * P0 / P1; testsOrNull = null: the events and areas fuzzGenerateFields left in the context) */
+JNIEXPORT jint JNICALL FN(randomExploreTestsAreas)(JNIEnv* e, jclass c, jlong h, jlong seedBase, jbyteArray testsOrNull, jlongArray areasOrNull,
+                                                  jintArray nEvOrNull, jint stride, jint nTests, jint executions, jintArray limits,
+                                                  jlongArray verdictsOrNull, jintArray flags) {
+  demi_limits lim;
+  (void)c;
+  if (limits_of(e, limits, &lim) || nTests < 0 || executions < 0 || stride < 0 || !flags || LEN(flags) < nTests ||
+      (verdictsOrNull && LEN(verdictsOrNull) < 2 * (int64_t)nTests * (int64_t)executions) ||
+      (testsOrNull && (!nEvOrNull || LEN(nEvOrNull) < nTests || LEN(testsOrNull) < 8 * (int64_t)nTests * (int64_t)stride)) ||
+      (areasOrNull && (!testsOrNull || LEN(areasOrNull) < (int64_t)nTests * (int64_t)stride)))
+    return DEMI_ERR_INVALID_ARG;
+  void* t = BYTES(testsOrNull);
+  void* ar = LONGS(areasOrNull);
+  void* ne = testsOrNull ? INTS(nEvOrNull) : NULL;
+  void* v = LONGS(verdictsOrNull);
+  void* fl = INTS(flags);
+  jint rc = (LOST(testsOrNull, t) || LOST(areasOrNull, ar) || (testsOrNull && LOST(nEvOrNull, ne)) || LOST(verdictsOrNull, v) || LOST(flags, fl))
+                ? DEMI_ERR_INVALID_ARG
+                : demi_random_explore_tests_areas(CTX(h), (uint64_t)seedBase, (const demi_ext_event*)t, (const uint64_t*)ar, (const uint32_t*)ne,
+                                                  (uint32_t)stride, (uint32_t)nTests, (uint32_t)executions, &lim, (demi_verdict*)v, (uint32_t*)fl);
+  PUT_INTS(flags, fl, 0);
+  PUT_LONGS(verdictsOrNull, v, 0);
+  if (testsOrNull) PUT_INTS(nEvOrNull, ne, JNI_ABORT);
+  PUT_LONGS(areasOrNull, ar, JNI_ABORT);
+  PUT_BYTES(testsOrNull, t, JNI_ABORT);
+  return rc;
+}
+
+/* fuzzCampaign with fieldGen; areas: long[255] (the violating test's payload areas) */
+JNIEXPORT jint JNICALL FN(fuzzCampaignFields)(JNIEnv* e, jclass c, jlong h, jint numEvents, jbyteArray prefix, jbyteArray postfixOrNull,
+                                             jlongArray weightBits, jbyteArray fieldGen, jlongArray campaign, jintArray limits,
+                                             jbyteArray events, jlongArray areas, jlongArray result) {
+  jni_fuzzer f;
+  demi_fuzz_field_gen g;
+  demi_limits lim;
+  demi_fuzz_campaign_params cp;
+  demi_fuzz_campaign_result res;
+  jlong o[9];
+  (void)c;
+  if (fuzzer_of(e, numEvents, prefix, postfixOrNull, weightBits, NULL, &f) || field_gen_of(e, fieldGen, &g) || limits_of(e, limits, &lim) ||
+      LEN(campaign) != 5 || LEN(result) != 9 || !events || LEN(events) < 8 * DEMI_MAX_EXT_EVENTS || !areas || LEN(areas) < DEMI_MAX_EXT_EVENTS)
+    return DEMI_ERR_INVALID_ARG;
+  memset(&cp, 0, sizeof cp);
+  {
+    void* cb = LONGS(campaign);
+    if (LOST(campaign, cb)) return DEMI_ERR_INVALID_ARG;
+    const jlong* q = (const jlong*)cb;
+    cp.test_seed_base = (uint64_t)q[0]; cp.exec_seed_base = (uint64_t)q[1]; cp.executions_per_test = (uint32_t)q[2];
+    cp.tests_per_launch = (uint32_t)q[3]; cp.max_tests = (uint32_t)q[4];
+    PUT_LONGS(campaign, cb, JNI_ABORT);
+  }
+  void* ev = BYTES(events);
+  void* ar = LONGS(areas);
+  jint rc = (LOST(events, ev) || LOST(areas, ar)) ? DEMI_ERR_INVALID_ARG
+            : demi_fuzz_campaign_fields(CTX(h), &f.par, &g, &cp, &lim, (demi_ext_event*)ev, (uint64_t*)ar, DEMI_MAX_EXT_EVENTS, &res);
+  PUT_LONGS(areas, ar, 0);
   PUT_BYTES(events, ev, 0);
   if (rc) return rc;
   o[0] = (jlong)res.found; o[1] = (jlong)res.test_index; o[2] = (jlong)res.exec_index; o[3] = (jlong)res.n_events; o[4] = (jlong)res.tests_run;

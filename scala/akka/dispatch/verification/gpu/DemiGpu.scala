@@ -67,6 +67,22 @@ object DemiGpu {
    *  exec_index, n_events, tests_run, launches, capacity_aborts, verdict flags | fingerprint << 32, verdict hash) */
   @native def fuzzCampaign(h: Long, numEvents: Int, prefix: Array[Byte], postfixOrNull: Array[Byte], weightBits: Array[Long], gen: Array[Byte],
                            campaign: Array[Long], limits: Array[Int], events: Array[Byte], result: Array[Long]): Int
+  /** The same for messages with more than two fields (a DEMI_MODEL_PAYLOADS table's external Sends): fieldGen = byte[296]
+   *  (demi_fuzz_field_gen: 1..8 alternatives (msg_type, target, n_fields, kind[6], arg[6]); the draw order is the alternative, the target,
+   *  then the fields 0, 1, .. in that order), and beside every array of events a long[] of as many 48-bit payload areas.
+   *  fuzzGenerateFields (demi_fuzz_generate_fields): areasOrNull = long[nTests * stride]; events AND areas stay in the context */
+  @native def fuzzGenerateFields(h: Long, numEvents: Int, prefix: Array[Byte], postfixOrNull: Array[Byte], weightBits: Array[Long],
+                                 fieldGen: Array[Byte], seedBase: Long, seedsOrNull: Array[Long], nTests: Int, eventsOrNull: Array[Byte],
+                                 areasOrNull: Array[Long], nEv: Array[Int], nBatchesOrNull: Array[Int]): Int
+  /** randomExploreTests for any table (demi_random_explore_tests_areas): areasOrNull = long[nTests * stride] beside testsOrNull (null with
+   *  tests: the areas are made of P0 / P1, as a load without staged areas does; testsOrNull = null: the resident events and areas) */
+  @native def randomExploreTestsAreas(h: Long, seedBase: Long, testsOrNull: Array[Byte], areasOrNull: Array[Long], nEvOrNull: Array[Int],
+                                      stride: Int, nTests: Int, executions: Int, limits: Array[Int], verdictsOrNull: Array[Long],
+                                      flags: Array[Int]): Int
+  /** fuzzCampaign with fieldGen (demi_fuzz_campaign_fields): areas = long[255], the violating test's payload areas beside its events */
+  @native def fuzzCampaignFields(h: Long, numEvents: Int, prefix: Array[Byte], postfixOrNull: Array[Byte], weightBits: Array[Long],
+                                 fieldGen: Array[Byte], campaign: Array[Long], limits: Array[Int], events: Array[Byte], areas: Array[Long],
+                                 result: Array[Long]): Int
   @native def replayGetKept(h: Long, maskOrNull: Array[Long], skip: Int, limits: Array[Int], verdict: Array[Long], kept: Array[Byte]): Int
   /** one round of STSSchedMinimizer.minimize, reduced on the device (demi_replay_removal_round): skip = the strategy's upcoming proposals,
    *  kept = byte[n recorded] (the executed-trace marks of proposal first_hit), result = long[6] (first_hit or -1, n_kept, retried, launches,

@@ -2,8 +2,8 @@
 export DEMI_EXPERIMENT=1     # the library reads its experiment / diagnostic variables only with this set (csrc/knobs.hpp)
 # tools/isa_diff.sh [<git rev>]  - which gfx950 kernels does the working tree compile to different instructions than <rev> (HEAD)?
 # No GPU needed.  The generic kernels of libdemi_gpu.so are compared symbol by symbol (device-only compilation of demi_gpu.hip,
-# disassembled), the kernels specialised for raft5 - the narrow table and the wide one, which alone gets the recording and
-# carried-generator modules compiled - by the .text of their code objects (demi_specialize_check under DEMI_JIT_DUMP).  A change that is meant to leave a hot kernel alone should show that kernel as SAME here before it goes to
+# disassembled), the kernels specialised for raft5 - the narrow table, the wide one, which alone gets the recording and
+# carried-generator modules compiled, and the one with akka-raft's field sets (DEMI_MODEL_PAYLOADS) - by the .text of their code objects (demi_specialize_check under DEMI_JIT_DUMP).  A change that is meant to leave a hot kernel alone should show that kernel as SAME here before it goes to
 # the GPU; scratch under gpurun_out/isa_diff (git-ignored).
 set -e
 REV=${1:-HEAD}
@@ -34,6 +34,8 @@ assert _native.__file__.startswith(root)
 _native.specialize_check(M.raft_model(5).to_struct())
 os.environ["DEMI_JIT_DUMP"] = out + "_wide"           # (the table tools/jit_stats.py --wide looks at)
 _native.specialize_check(M.raft_model(5, term0=1000, loglen0=300).to_struct())
+os.environ["DEMI_JIT_DUMP"] = out + "_fields"         # (a DEMI_MODEL_PAYLOADS table: the kernels that read payload areas)
+_native.specialize_check(M.raft_model(5, log_cap=8, real_fields=True).to_struct())
 PY
 python "$G/dump.py" "$G/wt" "$G/jitA"; python "$G/dump.py" "$ROOT" "$G/jitB"
 python - "$G" <<'PY'
@@ -78,7 +80,7 @@ a, b = named(per(G + '/disA.txt')), named(per(G + '/disB.txt'))
 for k in sorted(set(a) | set(b)):
     st = "SAME" if a.get(k) == b.get(k) else "NEW " if k not in a else "GONE" if k not in b else "DIFF"
     print("generic     %s %-110s %s -> %s" % (st, k[:110], a.get(k, ("-", 0))[1], b.get(k, ("-", 0))[1]))
-for table, suffix in (("raft5", ""), ("raft5 wide", "_wide")):
+for table, suffix in (("raft5", ""), ("raft5 wide", "_wide"), ("raft5 fields", "_fields")):
   for k in range(64):          # (every module either tree dumped: demi_gpu.hip JK_COUNT)
     h = []
     for t in "AB":
