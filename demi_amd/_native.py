@@ -718,12 +718,15 @@ class Context:
         self._check(lib().demi_dpor_set_traces(self._h, keys.ctypes.data if len(keys) else None, len(keys),
                                                init.ctypes.data if len(init) else None, len(init)))
 
-    def edit_distance_dpor_ddmin(self, externals, initial_trace, params, ip=None, cap=4096):
+    def edit_distance_dpor_ddmin(self, externals, initial_trace, params, ip=None, cap=4096, areas=None):
         """RunnerUtils.editDistanceDporDDMin natively (demi_edit_distance_dpor_ddmin: IncrementalDDMin over ResumableDPOR, every
         consultation K3 launches): (mcs indices, [(subsequence indices, passes, distance cap)] in consultation order,
-        [(cap, MCS size)] per pass, the reproducing interleaving or None, stats)."""
+        [(cap, MCS size)] per pass, the reproducing interleaving or None, stats).  areas: the payload area of every event of
+        `externals` (a DEMI_MODEL_PAYLOADS table); the library gathers them for every subsequence it consults.  None: P0 / P1."""
         import numpy as np
         ev = np.ascontiguousarray(externals, dtype=T.EXT_EVENT_DTYPE)
+        if areas is not None:
+            self.ext_payload_areas(areas)
         init = np.ascontiguousarray(initial_trace, dtype=T.DPOR_TRACE_DTYPE)
         ip = ip or T.IncDdminParams()
         mcs = np.zeros(4, dtype=np.uint64)

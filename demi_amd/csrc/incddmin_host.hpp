@@ -37,11 +37,14 @@ struct IncDdminResult {
 // Explore: int(const std::vector<demi_ext_event>& externals, const demi_dpor_search& search, std::unique_ptr<OrderedState>& state,
 //              demi_dpor_stats* stats, std::vector<demi_dpor_trace_entry>* first_violation_trace)
 //   one demi_dpor_explore over `externals` with ArvindDistanceOrdering and the caller's initial trace, on / leaving `state`.
+// sub_index (optional): before every call of `explore` it holds the ORIGINAL index of each event of `externals` - what a caller
+// needs to gather per-event data it keeps by original index (the payload areas of a DEMI_MODEL_PAYLOADS table's Sends).
 template <class Explore>
 class ResumableDpor {
  public:
-  ResumableDpor(const demi_ext_event* ext, uint32_t n_ext, uint32_t batch, uint32_t budget, Explore& explore)
-      : ext_(ext, ext + n_ext), batch_(batch ? batch : 256u), budget_(budget ? budget : (1u << 16)), explore_(explore) {}
+  ResumableDpor(const demi_ext_event* ext, uint32_t n_ext, uint32_t batch, uint32_t budget, Explore& explore,
+                std::vector<uint32_t>* sub_index = nullptr)
+      : ext_(ext, ext + n_ext), batch_(batch ? batch : 256u), budget_(budget ? budget : (1u << 16)), explore_(explore), sub_index_(sub_index) {}
   void set_max_distance(uint32_t d) { distance_ = d; }
   uint32_t instances() const { return (uint32_t)inst_.size(); }
   uint64_t interleavings() const { return interleavings_; }
@@ -54,7 +57,8 @@ class ResumableDpor {
     if (trace) *trace = &in.shortest;
     if (in.have_shortest) { *reproduced = true; return DEMI_OK; }             // stopIfViolationFound && shortestTraceSoFar != null
     std::vector<demi_ext_event> sub;
-    for (uint32_t i = 0; i < ext_.size(); i++) if (events.get(i)) sub.push_back(ext_[i]);
+    if (sub_index_) sub_index_->clear();
+    for (uint32_t i = 0; i < ext_.size(); i++) if (events.get(i)) { sub.push_back(ext_[i]); if (sub_index_) sub_index_->push_back(i); }
     demi_dpor_search srch;
     memset(&srch, 0, sizeof srch);
     srch.batch = batch_; srch.max_interleavings = budget_; srch.stop_if_violation = 1; srch.track_history = 1;
@@ -85,6 +89,7 @@ class ResumableDpor {
   std::vector<demi_ext_event> ext_;
   uint32_t batch_, budget_, distance_ = 0;
   Explore& explore_;
+  std::vector<uint32_t>* sub_index_;
   std::unordered_map<Mask256, Inst, Mask256Hash> inst_;
   uint64_t interleavings_ = 0;
 };
@@ -93,12 +98,13 @@ class ResumableDpor {
 // the Start / Send externals (convertToDPORTrace, DPORwHeuristics.scala:1279-1303: Kill / Partition / UnPartition are not part of
 // the minimization; WaitQuiescence only with ignore_quiescence = 0), then verify_mcs when the MCS is smaller than the view.
 template <class Explore>
-int edit_distance_dpor_ddmin(const demi_ext_event* ext, uint32_t n_ext, const demi_incddmin_params* ip, Explore&& explore, IncDdminResult* out) {
+int edit_distance_dpor_ddmin(const demi_ext_event* ext, uint32_t n_ext, const demi_incddmin_params* ip, Explore&& explore, IncDdminResult* out,
+                             std::vector<uint32_t>* sub_index = nullptr) {
   DdminDag dag(ext, n_ext, nullptr);
   Mask256 view;
   for (uint32_t i = 0; i < n_ext; i++)
     if (ext[i].kind == DEMI_EV_START || ext[i].kind == DEMI_EV_SEND || (ext[i].kind == DEMI_EV_WAIT_QUIESCENCE && !ip->ignore_quiescence)) view.set(i);
-  ResumableDpor<typename std::remove_reference<Explore>::type> oracle(ext, n_ext, ip->batch, ip->budget, explore);
+  ResumableDpor<typename std::remove_reference<Explore>::type> oracle(ext, n_ext, ip->batch, ip->budget, explore, sub_index);
   uint32_t distance = 0;
   oracle.set_max_distance(distance);
   if (ip->check_unmodified) {                                                  // IncrementalDDMin.minimize (:48-54)

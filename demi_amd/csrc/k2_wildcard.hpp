@@ -29,7 +29,9 @@
 // A wave takes lanes_per_wave candidates at a time (K2's small-launch shaping); every lane walks its own replay - lanes of a
 // wave deliver different messages to different receivers, so there is no lock step to keep.  A minimizer's batch is
 // 10 .. 10^3 candidates, each one replay's dependent chain long: this kernel is latency-bound.
-// filter_known_absents == 0 only; tables of up to 8 actors, narrow and DEMI_MODEL_WIDE (the host refuses the rest).
+// filter_known_absents == 0 only; tables of up to 8 actors: narrow, DEMI_MODEL_WIDE, and with DEMI_MODEL_PAYLOADS (the whole
+// 48-bit area in every message word formed, compared or recorded) and DEMI_MODEL_ARRAY (the array words are state words:
+// initialised, carved and hashed with the fields).  The host refuses the rest.
 #pragma once
 
 #include "sim_core.hpp"
@@ -69,8 +71,8 @@ struct K2WArgs {
 };
 
 __host__ __device__ inline size_t k2w_lds_bytes(uint32_t code_len, uint32_t n_ext, uint32_t n_hs, uint32_t n_actors, bool wide = WIDE_TU,
-                                                uint32_t hot = PEND_HOT) {
-  return tables_lds_bytes(code_len, n_ext, n_hs, wide, 0, false) + K2W_WAVES * lane_mem_wave_bytes(n_actors, true, hot, wide, DEMI_FX_CAP, 0);
+                                                uint32_t hot = PEND_HOT, uint32_t arr_words = ARR_WORDS) {
+  return tables_lds_bytes(code_len, n_ext, n_hs, wide, arr_words, false) + K2W_WAVES * lane_mem_wave_bytes(n_actors, true, hot, wide, DEMI_FX_CAP, arr_words);
 }
 
 // The candidates launch (k2_replay_wildcard_candidates below): work item = (candidate c, proposal j), c < n_cand, j <= n_drop.

@@ -123,6 +123,16 @@ class ArvindDistanceOrdering:
         return priority[0]
 
 
+def _check_areas(areas, externals):
+    """The payload areas of `externals` as a uint64 array, one per event; None stays None."""
+    if areas is None:
+        return None
+    areas = np.ascontiguousarray(areas, dtype=np.uint64)
+    if len(areas) != len(externals):
+        raise ValueError("%d payload areas for %d external events" % (len(areas), len(externals)))
+    return areas
+
+
 class DPORwHeuristics:
     """DPORwHeuristics(schedulerConfig, prioritizePendingUponDivergence=..., backtrackHeuristic=..., depth_bound=...,
     stopIfViolationFound=..., startFromBackTrackPoints=..., trackHistory=...) (DPORwHeuristics.scala:63-90)."""
@@ -193,14 +203,17 @@ class DPORwHeuristics:
                             lookingFor.code if lookingFor is not None else 0, self.p_max, self.max_pairs,
                             1 if self.prioritizePendingUponDivergence else 0)
 
-    def _run(self, externals, prefixes, params, shared=None):
+    def _run(self, externals, prefixes, params, shared=None, areas=None):
+        """areas: the payload area (T.pay_area) of every event of `externals`, for a DEMI_MODEL_PAYLOADS table whose external Sends
+        carry fields past P0 / P1; None: P0 / P1 of every Send.  A backend gets them as the keyword `areas` (only when given)."""
         from .distributed import sharded_batch
         if shared is None:
             shared = [0] * len(prefixes)
         items = list(zip(prefixes, shared))
         if self._backend is not None:
+            kw = {} if areas is None else {"areas": areas}
             fn = lambda part: self._backend(self.schedulerConfig.model, externals, [p for p, _ in part], params,
-                                            [s for _, s in part])
+                                            [s for _, s in part], **kw)
         else:
             if self._ctx is None:
                 from . import _native
@@ -208,7 +221,7 @@ class DPORwHeuristics:
                 self._ctx.model_load(self.schedulerConfig.model.to_struct())
                 if self.specialize or getattr(self.schedulerConfig.model, "compiled_only", False):     # (a wide table has no interpreter)
                     self._ctx.model_specialize()
-                self._ctx.dpor_load(externals)
+                self._ctx.dpor_load(externals, areas)
             fn = lambda part: self._ctx.dpor_batch([p for p, _ in part], params, [s for _, s in part])
         return sharded_batch(items, fn)
 
@@ -255,8 +268,10 @@ class DPORwHeuristics:
             self._seq += 1
 
     def explore(self, externals, lookingFor: Optional[ViolationFingerprint] = None,
-                max_interleavings: Optional[int] = None, stats: Optional[MinimizationStats] = None) -> Exploration:
+                max_interleavings: Optional[int] = None, stats: Optional[MinimizationStats] = None, areas=None) -> Exploration:
+        """areas: one payload area per event of `externals` (see _run)."""
         externals = np.ascontiguousarray(externals, dtype=T.EXT_EVENT_DTYPE)
+        areas = _check_areas(areas, externals)
         params = self._params(lookingFor)
         res = Exploration()
         shared = [0]
@@ -271,7 +286,7 @@ class DPORwHeuristics:
             frontier = [np.zeros(0, dtype=T.DPOR_TRACE_DTYPE)]        # first run: nextTrace is empty
         self._started = True
         while frontier:
-            verdicts, traces, pairs = self._run(externals, frontier, params, shared)
+            verdicts, traces, pairs = self._run(externals, frontier, params, shared, areas)
             res.rounds.append(len(frontier))
             if stats is not None:
                 stats.increment_replays(len(frontier))
@@ -302,7 +317,7 @@ class DPORwHeuristics:
         return res
 
     def explore_native(self, externals, lookingFor: Optional[ViolationFingerprint] = None, max_interleavings: int = 100000,
-                       reference_order: bool = False):
+                       reference_order: bool = False, areas=None):
         """The same exploration with the queue / explored-set bookkeeping run natively inside
         libdemi_gpu.so (demi_dpor_explore): identical rounds, verdicts and prefix lengths, two orders of
         magnitude less host time per interleaving than this Python loop.  Single rank only.
@@ -318,12 +333,13 @@ class DPORwHeuristics:
         if ordered and reference_order:
             raise NotImplementedError("the reference order runs with DefaultBacktrackOrdering, no cap and no initial trace")
         externals = np.ascontiguousarray(externals, dtype=T.EXT_EVENT_DTYPE)
+        areas = _check_areas(areas, externals)
         if self._ctx is None:
             self._ctx = _native.Context(self._device)
             self._ctx.model_load(self.schedulerConfig.model.to_struct())
             if self.specialize or getattr(self.schedulerConfig.model, "compiled_only", False):
                 self._ctx.model_specialize()
-            self._ctx.dpor_load(externals)
+            self._ctx.dpor_load(externals, areas)
         search = T.DporSearch(self.batch, max_interleavings, 1 if self.stopIfViolationFound else 0,
                               1 if self.trackHistory else 0, T.DPOR_ORDER_REFERENCE if reference_order else T.DPOR_ORDER_ROUNDS, 0,
                               T.DPOR_ORDERING_ARVIND if arvind else T.DPOR_ORDERING_DEFAULT,
@@ -350,8 +366,9 @@ class DPORwHeuristics:
         self.last_native_stats = stats
         return res
 
-    def test(self, events, violation_fingerprint: ViolationFingerprint, _stats: Optional[MinimizationStats] = None):
-        """TestOracle.test (:1193-1242): Some(trace of a matching violation) or None."""
+    def test(self, events, violation_fingerprint: ViolationFingerprint, _stats: Optional[MinimizationStats] = None, areas=None):
+        """TestOracle.test (:1193-1242): Some(trace of a matching violation) or None.  areas: one payload area per event of
+        `events` (a DEMI_MODEL_PAYLOADS table's external Sends with all their fields)."""
         if self.stopIfViolationFound and self.shortestTraceSoFar is not None:
             return self.shortestTraceSoFar
         if self.native:
@@ -360,7 +377,7 @@ class DPORwHeuristics:
             # BECAUSE of the budget (it used all of it, found nothing, points are still queued) is therefore continued from the
             # queue the library kept (resume, the ordered search) - or refused, where the library keeps no queue between calls:
             # "budget ran out" must never read as "the subsequence does not reproduce the violation".
-            res = self.explore_native(events, violation_fingerprint, max_interleavings=self.native_budget)
+            res = self.explore_native(events, violation_fingerprint, max_interleavings=self.native_budget, areas=areas)
             total = len(res.interleavings)
             while not res.violations and total and len(res.interleavings) >= self.native_budget and \
                     int(self.last_native_stats.queue_len) > 0 and not bool(self.last_native_stats.exhausted):
@@ -369,12 +386,12 @@ class DPORwHeuristics:
                     raise RuntimeError("DPORwHeuristics.test(native=True): %d interleavings explored, no violation, %d backtrack points "
                                        "still queued - raise native_budget (the search is not resumable without an ordering, a "
                                        "distance cap or an initial trace)" % (total, int(self.last_native_stats.queue_len)))
-                res = self.explore_native(events, violation_fingerprint, max_interleavings=self.native_budget)
+                res = self.explore_native(events, violation_fingerprint, max_interleavings=self.native_budget, areas=areas)
                 total += len(res.interleavings)
             if _stats is not None:
                 _stats.increment_replays(total)
         else:
-            res = self.explore(events, violation_fingerprint, stats=_stats)
+            res = self.explore(events, violation_fingerprint, stats=_stats, areas=areas)
         return res.interleavings[res.violations[0]].trace if res.violations else None
 
     def shutdown(self):

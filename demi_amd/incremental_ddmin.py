@@ -66,20 +66,31 @@ def dpor_initial_trace(trace: EventTrace, model=None) -> np.ndarray:
     return np.array(out, dtype=T.DPOR_TRACE_DTYPE)
 
 
+def _dpor_trace_indices(externals: np.ndarray, ignoreQuiescence: bool = True) -> List[int]:
+    """The events convertToDPORTrace keeps, as indices into `externals`."""
+    return [i for i, e in enumerate(externals)
+            if int(e["kind"]) in (T.EV_START, T.EV_SEND) or (int(e["kind"]) == T.EV_WAIT_QUIESCENCE and not ignoreQuiescence)]
+
+
 def convertToDPORTrace(externals: np.ndarray, ignoreQuiescence: bool = True) -> np.ndarray:
     """DPORwHeuristicsUtil.convertToDPORTrace (DPORwHeuristics.scala:1279-1303)."""
-    keep = [i for i, e in enumerate(externals)
-            if int(e["kind"]) in (T.EV_START, T.EV_SEND) or (int(e["kind"]) == T.EV_WAIT_QUIESCENCE and not ignoreQuiescence)]
-    return np.ascontiguousarray(externals[keep], dtype=T.EXT_EVENT_DTYPE)
+    return np.ascontiguousarray(externals[_dpor_trace_indices(externals, ignoreQuiescence)], dtype=T.EXT_EVENT_DTYPE)
 
 
 class ResumableDPOR:
     """IncrementalDeltaDebugging.scala:94-122: a TestOracle that keeps one DPOR instance per external-event
-    subsequence.  `events` are indices into `externals` (what the EventDag hands to the oracle)."""
+    subsequence.  `events` are indices into `externals` (what the EventDag hands to the oracle).  areas: the payload area of
+    every event of `externals` (EventTrace.ext_areas of a DEMI_MODEL_PAYLOADS table), gathered for each subsequence with the
+    index list convertToDPORTrace keeps; None: P0 / P1 of every Send."""
 
-    def __init__(self, ctor: Callable[[], DPORwHeuristics], externals: np.ndarray, ignoreQuiescence: bool = True):
+    def __init__(self, ctor: Callable[[], DPORwHeuristics], externals: np.ndarray, ignoreQuiescence: bool = True, areas=None):
+        if areas is not None:
+            areas = np.ascontiguousarray(areas, dtype=np.uint64)
+            if len(areas) != len(externals):
+                raise ValueError("%d payload areas for %d external events" % (len(areas), len(externals)))
         self.ctor = ctor
         self.externals = externals
+        self.areas = areas
         self.ignoreQuiescence = ignoreQuiescence
         self.subseqToDPOR: Dict[Tuple[int, ...], DPORwHeuristics] = {}
         self.currentMaxDistance = 0
@@ -97,8 +108,12 @@ class ResumableDPOR:
             self.subseqToDPOR[key] = self.ctor()
         dpor = self.subseqToDPOR[key]
         dpor.setMaxDistance(self.currentMaxDistance)
-        ext = convertToDPORTrace(self.externals[list(key)], self.ignoreQuiescence)
-        return dpor.test(ext, violation_fingerprint, stats)
+        sub = self.externals[list(key)]
+        ext = convertToDPORTrace(sub, self.ignoreQuiescence)
+        if self.areas is None:
+            return dpor.test(ext, violation_fingerprint, stats)
+        kept = _dpor_trace_indices(sub, self.ignoreQuiescence)
+        return dpor.test(ext, violation_fingerprint, stats, areas=self.areas[[key[k] for k in kept]])
 
     def shutdown(self):
         for d in self.subseqToDPOR.values():
@@ -174,7 +189,8 @@ def editDistanceDporDDMin(schedulerConfig: SchedulerConfig, trace: EventTrace, v
             par = T.DporParams(0, len(initialTrace), 1, violation.code, 64, 4096, 1)
             ip = T.IncDdminParams(max_max_distance=maxMaxDistance, stop_at_size=stopAtSize, check_unmodified=0,
                                   ignore_quiescence=1 if ignoreQuiescence else 0, verify_mcs=1, batch=batch)
-            mcs, consulted, passes, vtrace, st = ctx.edit_distance_dpor_ddmin(trace.original_externals, initialTrace, par, ip)
+            mcs, consulted, passes, vtrace, st = ctx.edit_distance_dpor_ddmin(trace.original_externals, initialTrace, par, ip,
+                                                                              areas=getattr(trace, "ext_areas", None))
         finally:
             ctx.close()
         res = NativeIncrementalDDMin(consulted, passes, st)
@@ -197,7 +213,7 @@ def editDistanceDporDDMin(schedulerConfig: SchedulerConfig, trace: EventTrace, v
     keep = tuple(i for i in dag.events if int(externals[i]["kind"]) in (T.EV_START, T.EV_SEND) or
                  (int(externals[i]["kind"]) == T.EV_WAIT_QUIESCENCE and not ignoreQuiescence))
     view = EventDagView(dag, keep)
-    resumableDPOR = ResumableDPOR(dporConstructor, externals, ignoreQuiescence)
+    resumableDPOR = ResumableDPOR(dporConstructor, externals, ignoreQuiescence, areas=getattr(trace, "ext_areas", None))
     ddmin = IncrementalDDMin(resumableDPOR, stopAtSize=stopAtSize, maxMaxDistance=maxMaxDistance, stats=stats)
     try:
         mcs = ddmin.minimize(view, violation)

@@ -54,6 +54,11 @@ def getFingerprintedDeliveries(trace: EventTrace) -> List[Key]:
     return [k for _, k, _ in deliveries(trace)]
 
 
+def _areas_of(trace: EventTrace, mcs) -> Optional[np.ndarray]:
+    """trace.ext_areas when `mcs` are the externals they belong to (one area per external), else None."""
+    return trace.ext_areas if trace.ext_areas is not None and len(trace.ext_areas) == len(mcs) else None
+
+
 def executed_trace(trace: EventTrace, kept: np.ndarray, externals: Optional[np.ndarray] = None,
                    subseq: Optional[Sequence[int]] = None) -> EventTrace:
     """The EventTrace STSScheduler.test returns on success (STSScheduler.scala:286-292) from the
@@ -62,6 +67,8 @@ def executed_trace(trace: EventTrace, kept: np.ndarray, externals: Optional[np.n
     setOriginalExternalEvents(mcs) (RunnerUtils.scala:698) and ext_idx renumbered to it."""
     ev = trace.events[np.asarray(kept, dtype=bool)].copy()
     ext = trace.original_externals if externals is None else externals
+    # (the payload areas of a DEMI_MODEL_PAYLOADS table's externals follow the externals that are kept)
+    areas = trace.ext_areas if externals is None else None
     if subseq is not None:
         subseq = sorted(int(i) for i in subseq)
         remap = np.full(256, 255, dtype=np.uint8)
@@ -69,7 +76,8 @@ def executed_trace(trace: EventTrace, kept: np.ndarray, externals: Optional[np.n
             remap[old] = new
         ev["ext_idx"] = remap[ev["ext_idx"]]
         ext = trace.original_externals[subseq].copy()
-    return EventTrace(ev, ext)
+        areas = None if trace.ext_areas is None else np.asarray(trace.ext_areas)[subseq].copy()
+    return EventTrace(ev, ext, areas)
 
 
 # ------------------------------------------------------------------ removal strategies
@@ -89,7 +97,7 @@ class RemovalStrategy:
         i = self.next_index(lastFailingTrace, alreadyRemoved, violationTriggered)
         if i is None:
             return None
-        return EventTrace(np.delete(lastFailingTrace.events, i), lastFailingTrace.original_externals)
+        return EventTrace(np.delete(lastFailingTrace.events, i), lastFailingTrace.original_externals, lastFailingTrace.ext_areas)
 
     def clone(self) -> "RemovalStrategy":
         raise NotImplementedError
@@ -286,7 +294,7 @@ class StsRemovalOracle:
         events, sizes, batches, st = self._ctx.minimize_internals(self._limits(violation), T.IntminParams(code, max(1, int(max_batch))))
         stats.increment_replays(int(st.total_replays))
         self.native_stats, self.native_sizes, self.native_batches = st, sizes, batches
-        return stats, EventTrace(events, mcs)
+        return stats, EventTrace(events, mcs, _areas_of(verified_mcs, mcs))
 
     def shutdown(self):
         self._ctx.close()
@@ -312,7 +320,8 @@ class STSSchedMinimizer:
         self.internal_sizes: List[int] = []       # record_internal_size after every (sequential) replay
 
     def minimize(self) -> Tuple[MinimizationStats, EventTrace]:
-        lastFailingTrace = EventTrace(self.verified_mcs.events, self.mcs)
+        areas = _areas_of(self.verified_mcs, self.mcs)
+        lastFailingTrace = EventTrace(self.verified_mcs.events, self.mcs, areas)
         lastFailingSize = countMsgEvents(lastFailingTrace)
         prunedOverall: Counter = Counter()
         violationTriggered = False
@@ -351,7 +360,7 @@ class STSSchedMinimizer:
             prunedThisRun = Counter(getFingerprintedDeliveries(lastFailingTrace)) - \
                 Counter(getFingerprintedDeliveries(trace))
             prunedOverall += prunedThisRun
-            lastFailingTrace = EventTrace(trace.events, self.mcs)
+            lastFailingTrace = EventTrace(trace.events, self.mcs, areas)
             lastFailingSize = countMsgEvents(lastFailingTrace)
             self.internal_sizes.append(lastFailingSize)
             violationTriggered = True

@@ -387,7 +387,7 @@ class StsWildcardOracle:
             return None
         ev = self._trace.events
         ignored = {int(i) for i in np.nonzero((ev["kind"] == T.REC_MSG_EVENT) & np.asarray(present, dtype=bool) & (kept == 0))[0]}
-        return EventTrace(rec, self._trace.original_externals), ignored
+        return EventTrace(rec, self._trace.original_externals, self._trace.ext_areas), ignored
 
     def shutdown(self):
         self._ctx.close()
@@ -408,7 +408,9 @@ class WildcardMinimizer:
                  max_batch: int = 1 << 14, oracle=None, device: int = 0, p_max: int = 64):
         self.schedulerConfig = schedulerConfig
         self.mcs = mcs
-        self.trace = EventTrace(trace.events, mcs)
+        # (the payload areas of a DEMI_MODEL_PAYLOADS table's externals stay with the trace: `mcs` are its externals)
+        self.ext_areas = trace.ext_areas if trace.ext_areas is not None and len(trace.ext_areas) == len(mcs) else None
+        self.trace = EventTrace(trace.events, mcs, self.ext_areas)
         self.violation = violation
         self.skipClockClusters = skipClockClusters
         self.resolutionStrategy = resolutionStrategy if resolutionStrategy is not None else BackTrackStrategy()
@@ -485,7 +487,7 @@ class WildcardMinimizer:
             got = self.oracle.executed(cands[j], self.violation)
             assert got is not None, "batched and single replay of the same candidate disagree"
             ret, ignoredAbsentIndices = got
-            ret = EventTrace(ret.events, self.mcs)
+            ret = EventTrace(ret.events, self.mcs, self.ext_areas)
             if len(ret.events) <= len(minTrace.events):
                 minTrace = ret
             last = (True, frozenset(id_of_rec[i] for i in ignoredAbsentIndices))
@@ -559,7 +561,9 @@ class WildcardTestOracle:
         remap = np.full(256, 255, dtype=np.uint8)
         remap[list(events)] = np.arange(len(events), dtype=np.uint8)
         ev["ext_idx"] = remap[ev["ext_idx"]]
-        return EventTrace(ev, self.originalTrace.original_externals[list(events)].copy())
+        areas = self.originalTrace.ext_areas
+        return EventTrace(ev, self.originalTrace.original_externals[list(events)].copy(),
+                          None if areas is None else np.asarray(areas)[list(events)].copy())
 
     def test(self, events, violation: ViolationFingerprint, stats: Optional[MinimizationStats] = None, fetch: bool = True):
         """Some(trace) / None as the Scala; fetch=False answers True in place of the trace (DDMin only asks whether it is None)."""

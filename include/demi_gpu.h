@@ -397,7 +397,9 @@ int demi_trace_load(demi_ctx* ctx, const demi_ext_event* events, uint32_t n_even
  * area (DEMI_MODEL_PAYLOADS above: field k in bits [k * w, (k + 1) * w)) of external event i of the trace that the NEXT
  * demi_trace_load / demi_dpor_load of this context loads - read for its Send events only, n must equal that load's count, the
  * load consumes it (a later load without a new call takes the fields from the events again: P0, P1, the others 0).  A table with
- * two payload fields ignores it.  demi_replay_load needs none: the recorded MsgSend of an external message carries its area
+ * two payload fields ignores it.  Staged before demi_edit_distance_dpor_ddmin(externals, n_ext, ...) the areas are those of
+ * `externals` (n must equal n_ext): that call keeps them and stages, for every subsequence it loads, the areas of the events it
+ * kept (see there).  demi_replay_load needs none: the recorded MsgSend of an external message carries its area
  * (demi_rec_event p0 / p1 / p_hi), and that is what a replay enqueues.  NULL, 0: forget a staged array. */
 int demi_ext_payload_areas(demi_ctx* ctx, const uint64_t* areas, uint32_t n);
 
@@ -545,8 +547,15 @@ typedef enum {
 } demi_wildcard_policy;
 /* The selectors of the execution loaded by demi_replay_load, one per recorded event (entries of events that are not
  * MsgEvents are ignored): type_sets[i] bit t = message type t matches, 0 = the exact delivery of demi_replay_batch;
- * policies[i] a demi_wildcard_policy.  One load serves every candidate of a Clusterizer.  DEMI_ERR_INVALID_ARG: a table of
- * more than 8 actors, a DEMI_MODEL_PAYLOADS or DEMI_MODEL_ARRAY table (not built; never replayed with other semantics). */
+ * policies[i] a demi_wildcard_policy.  One load serves every candidate of a Clusterizer.  LIMITS of the wildcard replays
+ * (this call, demi_replay_wildcard_batch / _get_trace / _candidates, demi_wildcard_ddmin): a table of more than 8 actors is
+ * refused here (DEMI_ERR_INVALID_ARG; not built, never replayed with other semantics), limits->filter_known_absents must be 0.
+ * DEMI_MODEL_WIDE, DEMI_MODEL_PAYLOADS and DEMI_MODEL_ARRAY tables are replayed - a wildcard matches on the type set and ignores
+ * every field, an exact selector (type set 0) compares the whole message, every field of the 48-bit payload area included, and
+ * the executed trace records what was delivered with all its fields (p0 / p1 / p_hi) - but, like every kernel of such a table,
+ * only as compiled code: without a successful demi_model_specialize the launch fails with DEMI_ERR_INVALID_MODEL ("runs only
+ * as a compiled table").  A launch whose tables and per-lane state (the arrays' words included) exceed 160 KiB of LDS is refused
+ * on the host ("wildcard replay: LDS budget exceeded"), before anything is launched. */
 int demi_replay_wildcard_load(demi_ctx* ctx, const uint32_t* type_sets /* [n_rec] */, const uint8_t* policies /* [n_rec] */);
 /* n candidates: masks as in demi_replay_batch (NULL: every external kept); present[c] is a bitmask over the recorded events
  * (ceil(n_rec / 64) words, bit i of word i / 64): a MsgEvent whose bit is 0 is not part of candidate c's trace (with all
@@ -906,7 +915,12 @@ typedef struct demi_incddmin_stats {
   uint32_t pass_distance[16];   /* per pass (the first 16): its cap, and the MCS size after it */
   uint32_t pass_mcs_len[16];
 } demi_incddmin_stats;
-/* out_mcs: bit i = external event i is in the MCS.  out_consulted [cap][4] / out_passed [cap] / out_distance [cap] (may be
+/* A DEMI_MODEL_PAYLOADS table's external Sends with all their fields: the areas staged with demi_ext_payload_areas(areas, n)
+ * before this call are the areas of `externals` - n != n_ext is DEMI_ERR_INVALID_ARG, with both numbers in the message.  The call
+ * takes them out of the context, keeps them for its duration indexed by ORIGINAL external index, and before every
+ * demi_dpor_load of a subsequence stages areas[original index of the k-th kept event] as that load's k-th area; nothing stays
+ * staged afterwards.  With nothing staged the areas are P0 / P1 of every Send, the other fields 0, as demi_trace_load makes them.
+ * out_mcs: bit i = external event i is in the MCS.  out_consulted [cap][4] / out_passed [cap] / out_distance [cap] (may be
  * NULL): every DDMin consultation in order - the subsequence, whether it "passes" (no violation), the cap it ran under.
  * out_violation_trace [DEMI_DPOR_MAX_TRACE] (may be NULL): the interleaving that reproduces the violation on the MCS. */
 int demi_edit_distance_dpor_ddmin(demi_ctx* ctx, const demi_ext_event* externals, uint32_t n_ext,

@@ -424,6 +424,8 @@ object GpuEditDistanceDporDDMin {
       val dporParams = Array(0, init.length / 16, 1, lowering.fingerprintCode(violation), 64, 4096, 1)
       val params = Array(maxMaxDistance, stopAtSize, 0, if (ignoreQuiescence) 1 else 0, 1, batch, 0)
       val mcs = new Array[Long](4); val vt = new Array[Byte](16 * 256); val st = new Array[Long](40)
+      // external Sends with all their fields: staged for `ext` as a whole, the library gathers them for every subsequence it consults
+      if (lowering.model.payloads > 2) check(h, extPayloadAreas(h, FlatEvents.packAreas(ext, lowering)))
       check(h, DemiGpu.editDistanceDporDDMin(h, FlatEvents.pack(ext, lowering), init, dporParams, params, mcs, null, null, null, vt, st))
       val out = stats.getOrElse(new MinimizationStats)
       (0L until st(0)).foreach(_ => out.increment_replays())
