@@ -22,7 +22,7 @@ EXPORTS = ["demi_ctx_create", "demi_ctx_destroy", "demi_last_error", "demi_versi
            "demi_replay_wildcard_candidates", "demi_wildcard_ddmin",
            "demi_fuzz_stride", "demi_fuzz_generate", "demi_random_explore_tests", "demi_fuzz_campaign",
            "demi_fuzz_generate_fields", "demi_random_explore_tests_areas", "demi_fuzz_campaign_fields",
-           "demi_replay_removal_round", "demi_minimize_internals"]
+           "demi_replay_removal_round", "demi_minimize_internals", "demi_replay_wildcard_round", "demi_minimize_wildcards"]
 
 _lib = None
 ALLGATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t)     # demi_allgather_fn
@@ -161,6 +161,10 @@ def lib():
                                             C.POINTER(T.RemovalRoundResult)]
     L.demi_minimize_internals.argtypes = [C.c_void_p, C.POINTER(T.Limits), C.POINTER(T.IntminParams), C.c_void_p, C.c_uint32,
                                           C.POINTER(C.c_uint32), C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.POINTER(T.IntminStats)]
+    L.demi_replay_wildcard_round.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(T.Limits), C.c_void_p,
+                                             C.POINTER(T.WildcardRoundResult)]
+    L.demi_minimize_wildcards.argtypes = [C.c_void_p, C.POINTER(T.Limits), C.POINTER(T.WcminParams), C.c_void_p, C.c_uint32,
+                                          C.POINTER(C.c_uint32), C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.POINTER(T.WcminStats)]
     # every export has its argument types declared: an undeclared one would silently truncate pointers to 32 bits
     for name in EXPORTS:
         fn = getattr(L, name)
@@ -630,6 +634,40 @@ class Context:
         self._check(lib().demi_replay_wildcard_get_trace(self._h, mp, (pw if pw.size else dummy).ctypes.data, C.byref(limits),
                                                          C.byref(v), kept.ctypes.data, rec.ctypes.data, cap, C.byref(n_out)))
         return v, kept[:n_rec], rec[:n_out.value].copy()
+
+    def replay_wildcard_round(self, present, limits, mask=None):
+        """One round of WildcardMinimizer.doMinimize (demi_replay_wildcard_round): the proposals `present` (bool[n, n_rec]) over the
+        loaded execution and selectors, reduced on the device.  (WildcardRoundResult, uint8[n_rec] kept marks of proposal
+        first_hit - None without a hit)."""
+        import numpy as np
+        n_rec = int(lib().demi_replay_recorded_len(self._h))
+        pw = self._present_words(present, n_rec)
+        mp = None
+        if mask is not None:
+            mask = np.ascontiguousarray(mask, dtype=np.uint64).reshape(4)
+            mp = mask.ctypes.data
+        kept = np.zeros(max(n_rec, 1), dtype=np.uint8)
+        res = T.WildcardRoundResult()
+        dummy = np.zeros(1, dtype=np.uint64)
+        self._check(lib().demi_replay_wildcard_round(self._h, mp, (pw if pw.size else dummy).ctypes.data, len(pw), C.byref(limits),
+                                                     kept.ctypes.data, C.byref(res)))
+        return res, (kept[:n_rec] if res.first_hit != 0xFFFFFFFF else None)
+
+    def minimize_wildcards(self, limits, params, cap=None):
+        """WildcardMinimizer.minimize on the loaded replay, natively (demi_minimize_wildcards): (minimized recorded events,
+        record_internal_size sequence, proposals per round, WcminStats).  The context's loaded execution is the minimized one
+        afterwards, without selectors - also when the call raises on a capacity (then the last adopted trace)."""
+        import numpy as np
+        cap = T.MAX_REC_EVENTS if cap is None else int(cap)
+        out = np.zeros(max(cap, 1), dtype=T.REC_EVENT_DTYPE)
+        sizes = np.zeros(2 * T.MAX_REC_EVENTS + 4, dtype=np.uint32)    # (a replay per delivery and pass at the most, and the fencepost)
+        batches = np.zeros(2 * T.MAX_REC_EVENTS + 4, dtype=np.uint32)
+        n = C.c_uint32(0)
+        st = T.WcminStats()
+        self._check(lib().demi_minimize_wildcards(self._h, C.byref(limits), C.byref(params), out.ctypes.data, cap, C.byref(n),
+                                                  sizes.ctypes.data, len(sizes), batches.ctypes.data, len(batches), C.byref(st)))
+        return out[:n.value].copy(), [int(x) for x in sizes[:min(len(sizes), st.sizes)]], \
+            [int(x) for x in batches[:min(len(batches), st.rounds)]], st
 
     def _base_present(self, base_present):
         import numpy as np

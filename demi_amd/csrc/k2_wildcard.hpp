@@ -93,6 +93,8 @@ struct K2WCandArgs { K2WArgs a; K2WCand c; };
 // The body of both kernels is k2_wildcard_body.hpp, included once per kernel with K2W_CAND 0 / 1 (a textual include, so that
 // k2_replay_wildcard stays the code it was: same parameter accesses, same instructions).  K2W_CAND 1: args.n counts work items,
 // args.masks is [n_cand][4], args.present / kept / rec_out are unused, args.out is the full [n_cand][1 + n_drop] plane.
+// k2_wildcard_round.hpp includes it a third time, K2W_CAND 0 with K2W_ROUND 1: the rows and the kept plane of this kernel, the
+// executed length and the reduction of the candidates kernel (one key / first_ovf word per launch).
 __global__ __launch_bounds__(K2W_WAVES * 64) void k2_replay_wildcard(const K2WArgs args) {
   const K2WCand cand = {};
 #define K2W_CAND 0

@@ -1,7 +1,14 @@
-// k2_wildcard_body.hpp - the body of k2_replay_wildcard (k2_wildcard.hpp) and k2_replay_wildcard_candidates
-// (k2_wildcard_cand.hpp).  NOT a header of its own: it is included inside a kernel that has `args` (K2WArgs), `cand` (K2WCand)
-// and the macro K2W_CAND (0 / 1) in scope.  No include guard: once per kernel.
+// k2_wildcard_body.hpp - the body of k2_replay_wildcard (k2_wildcard.hpp), k2_replay_wildcard_candidates
+// (k2_wildcard_cand.hpp) and k2_replay_wildcard_round (k2_wildcard_round.hpp).  NOT a header of its own: it is included inside a
+// kernel that has `args` (K2WArgs), `cand` (K2WCand) and the macro K2W_CAND (0 / 1) in scope; K2W_ROUND (1: the round kernel,
+// with K2W_CAND 0) is optional.  No include guard: once per kernel.
+#ifndef K2W_ROUND
+#define K2W_ROUND 0
+#define K2W_ROUND_DEFAULTED 1
+#endif
   constexpr bool CAND = K2W_CAND != 0;
+  constexpr bool ROUND = K2W_ROUND != 0;   // explicit presence rows and the kept plane as the batch kernel, the executed length
+  constexpr bool XLEN = CAND || ROUND;     // counted as the candidates kernel does, the launch reduced into cand.key[0] / first_ovf[0]
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   Tables t;
   unsigned char* wave_base = tables_load(t, smem, args.model, args.ext, args.n_ext, args.exists);
@@ -42,9 +49,9 @@
     const word_t w_ = (WORD);                                                                 \
     if (n_pend >= PMAX) { flags |= DEMI_V_PENDING_OVF; }                                      \
     else {                                                                                    \
-      /* (candidates: the sequence number carries whether the message is an external MsgSend; the order is the ids') */ \
-      pend_store(mem, n_pend, w_); aux_store(mem, n_pend, CAND ? ((next_id << 1) | ((FL) == 1 ? 1u : 0u)) : next_id); n_pend++; \
-      if (CAND && (FL) == 1) xlen++;                                                          \
+      /* (candidates, round: the sequence number carries whether the message is an external MsgSend; the order is the ids') */ \
+      pend_store(mem, n_pend, w_); aux_store(mem, n_pend, XLEN ? ((next_id << 1) | ((FL) == 1 ? 1u : 0u)) : next_id); n_pend++; \
+      if (XLEN && (FL) == 1) xlen++;                                                          \
       REC_PUSH(DEMI_REC_MSG_SEND, w_src(w_), w_dst(w_), w_type(w_), w_area(w_), (FL), (EXT), next_id); \
       next_id++;                                                                              \
     }                                                                                         \
@@ -67,13 +74,13 @@
     uint32_t xlen = 0;
     uint64_t m0, m1, m2, m3;
     if (args.masks) {
-      const uint64_t* mk = args.masks + (CAND ? cand_c : sched) * 4;
+      const uint64_t* mk = args.masks + (CAND ? cand_c : ROUND ? 0ull : sched) * 4;      // (round: one row for all)
       m0 = mk[0]; m1 = mk[1]; m2 = mk[2]; m3 = mk[3];
     } else {
       m0 = m1 = m2 = m3 = ~0ull;
     }
     const uint64_t* present = CAND ? cand.base_present : args.present + sched * (uint64_t)args.present_words;
-    demi_rec_event* rec = (!CAND && args.rec_out) ? args.rec_out + sched * (uint64_t)args.rec_cap : nullptr;
+    demi_rec_event* rec = (!CAND && !ROUND && args.rec_out) ? args.rec_out + sched * (uint64_t)args.rec_cap : nullptr;
     uint64_t hash = 0xCBF29CE484222325ULL;
     uint64_t app_rng = jr_seed(0);
     Net net;
@@ -125,7 +132,7 @@
           cur++;
           cur_skip();
           if (!CAND && args.kept) args.kept[sched * NX + idx - 1] = 1;
-          if (CAND) xlen++;
+          if (XLEN) xlen++;
           REC_PUSH(kind, two ? a : 0u, two ? b : a, 0, 0, 0, ext, 0);
           if (kind == DEMI_REC_SPAWN) { net.inaccessible &= ~(1u << a); net.killed &= ~(1u << a); blocked &= ~(1u << a); }
           else if (kind == DEMI_REC_KILL) { net.killed |= 1u << a; net.inaccessible |= 1u << a; }
@@ -180,7 +187,7 @@
       const uint32_t type = w_type(w), me = w_dst(w);
       count++;
       hash_step(hash, w);
-      if (CAND) xlen += 2u - (wid & 1u);
+      if (XLEN) xlen += 2u - (wid & 1u);
       REC_PUSH(DEMI_REC_MSG_EVENT, w_src(w), me, type, w_area(w), 0, 255, wid);
       {
         // Instrumenter retrigger of a repeating timer (Instrumenter.scala:1008-1016)
@@ -264,9 +271,18 @@
       if (flags & DEMI_OVF_ANY) atomicMin(&cand.first_ovf[cand_c], cand_j);
       else if (viol) atomicMin(&cand.key[cand_c], ((unsigned long long)cand_j << 32) | (unsigned long long)xlen);
     }
+    if (ROUND) {
+      // the round's record: the lowest reproducing proposal with its executed length, and the lowest aborted one
+      if (flags & DEMI_OVF_ANY) atomicMin(&cand.first_ovf[0], (uint32_t)sched);
+      else if (viol) atomicMin(&cand.key[0], ((unsigned long long)sched << 32) | (unsigned long long)xlen);
+    }
   }
 #undef IN_MASK
 #undef EXP_WORD
 #undef TIMER_BIT
 #undef PEND_APPEND
 #undef REC_PUSH
+#ifdef K2W_ROUND_DEFAULTED
+#undef K2W_ROUND
+#undef K2W_ROUND_DEFAULTED
+#endif

@@ -22,7 +22,7 @@ MAX_CODE = 1024
 MAX_TIMER_TYPES = 4
 MAX_EXT_EVENTS = 255
 MAX_REC_EVENTS = 16384
-ABI_VERSION = 4             # DEMI_ABI_VERSION of include/demi_gpu.h (struct-layout generation)
+ABI_VERSION = 5             # DEMI_ABI_VERSION of include/demi_gpu.h (struct-layout generation)
 MAX_PENDING = 128          # DEMI_MAX_PENDING
 
 # demi_status
@@ -244,6 +244,38 @@ class IntminStats(C.Structure):
     _fields_ = [("total_replays", C.c_uint64), ("replays_run", C.c_uint64), ("rounds", C.c_uint32), ("launches", C.c_uint32),
                 ("adoptions", C.c_uint32), ("retried", C.c_uint32), ("unignorable", C.c_uint32), ("deliveries_before", C.c_uint32),
                 ("deliveries_after", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class WildcardRoundResult(C.Structure):
+    """demi_wildcard_round_result"""
+    _fields_ = [("first_hit", C.c_uint32), ("executed_len", C.c_uint32), ("n_kept", C.c_uint32), ("retried", C.c_uint32),
+                ("launches", C.c_uint32), ("reserved", C.c_uint32), ("verdict", Verdict)]
+
+
+CLUSTER_CLOCK = 0             # demi_clustering
+CLUSTER_SINGLETON = 1
+CLUSTER_CLOCK_THEN_SINGLETON = 2
+
+
+class WcminParams(C.Structure):
+    """demi_wcmin_params"""
+    _fields_ = [("clustering", C.c_uint32), ("policy", C.c_uint32), ("skip_clock_clusters", C.c_uint32), ("max_batch", C.c_uint32),
+                ("clock_increment_types", C.c_uint32), ("clock_field", C.c_uint8 * 32)]
+
+    def __init__(self, clustering=CLUSTER_CLOCK, policy=1, skip_clock_clusters=0, max_batch=0, clock_increment_types=(), clock_field=None):
+        """clock_increment_types / clock_field as model.Model holds them: a set of message types, {type: payload field}."""
+        inc = sum(1 << int(t) for t in clock_increment_types) if not isinstance(clock_increment_types, int) else clock_increment_types
+        fields = (C.c_uint8 * 32)(*([255] * 32))
+        for t, k in (clock_field or {}).items():
+            fields[int(t)] = int(k)
+        super().__init__(clustering, policy, int(bool(skip_clock_clusters)), max_batch, inc, fields)
+
+
+class WcminStats(C.Structure):
+    """demi_wcmin_stats"""
+    _fields_ = [("total_replays", C.c_uint64), ("replays_run", C.c_uint64), ("rounds", C.c_uint32), ("launches", C.c_uint32),
+                ("adoptions", C.c_uint32), ("retried", C.c_uint32), ("sizes", C.c_uint32), ("reserved", C.c_uint32),
+                ("deliveries_before", C.c_uint32), ("deliveries_after", C.c_uint32)]
 
 
 class WildcardDdminResult(C.Structure):

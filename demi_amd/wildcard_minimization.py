@@ -389,6 +389,29 @@ class StsWildcardOracle:
         ignored = {int(i) for i in np.nonzero((ev["kind"] == T.REC_MSG_EVENT) & np.asarray(present, dtype=bool) & (kept == 0))[0]}
         return EventTrace(rec, self._trace.original_externals, self._trace.ext_areas), ignored
 
+    def minimize_native(self, mcs: np.ndarray, trace: EventTrace, violation: ViolationFingerprint, clusteringStrategy: str,
+                        resolutionStrategy: AmbiguityResolutionStrategy, skipClockClusters: bool = False,
+                        stats: Optional[MinimizationStats] = None, max_batch: int = 1 << 14) -> Tuple[MinimizationStats, EventTrace]:
+        """WildcardMinimizer(...).minimize() as one call of the library (demi_minimize_wildcards).  Of `resolutionStrategy` only
+        the policy is used; the clock hooks are the model's.  The library lowers the selectors itself."""
+        codes = {ClusteringStrategy.ClockClusterizer: T.CLUSTER_CLOCK, ClusteringStrategy.SingletonClusterizer: T.CLUSTER_SINGLETON,
+                 ClusteringStrategy.ClockThenSingleton: T.CLUSTER_CLOCK_THEN_SINGLETON}
+        if clusteringStrategy not in codes:
+            raise ValueError("unknown clustering strategy %r" % (clusteringStrategy,))
+        model = self.schedulerConfig.model
+        stats = stats or MinimizationStats()
+        areas = trace.ext_areas if trace.ext_areas is not None and len(trace.ext_areas) == len(mcs) else None
+        self._ctx.replay_load(mcs, trace.events)
+        self._trace = None            # the call replaces the context's loaded execution (also when it raises)
+        par = T.WcminParams(codes[clusteringStrategy], resolutionStrategy.policy, skipClockClusters, max(1, int(max_batch)),
+                            model.clock_increment_types, model.clock_field)
+        events, sizes, batches, st = self._ctx.minimize_wildcards(self._limits(violation), par)
+        stats.increment_replays(int(st.total_replays))
+        self.launches += int(st.launches)
+        self.batches.extend(batches)
+        self.native_stats, self.native_sizes, self.native_batches = st, sizes, batches
+        return stats, EventTrace(events, mcs, areas)
+
     def shutdown(self):
         self._ctx.close()
 
@@ -400,13 +423,16 @@ class ClusteringStrategy:
 
 class WildcardMinimizer:
     """WildcardMinimizer.scala:44-242 with TestScheduler.STSSched.  `oracle`: a StsWildcardOracle (created, and shut down, here
-    when None).  `max_batch` bounds how many of the clusterizer's upcoming proposals are replayed per launch."""
+    when None).  `max_batch` bounds how many of the clusterizer's upcoming proposals are replayed per launch.  native: minimize()
+    is ONE call of the library (demi_minimize_wildcards: same trace, same stats.total_replays, internal_sizes and batches; the
+    oracle must be a StsWildcardOracle)."""
 
     def __init__(self, schedulerConfig: SchedulerConfig, mcs: np.ndarray, trace: EventTrace, violation: ViolationFingerprint,
                  skipClockClusters: bool = False, resolutionStrategy: Optional[AmbiguityResolutionStrategy] = None,
                  clusteringStrategy: str = ClusteringStrategy.ClockClusterizer, stats: Optional[MinimizationStats] = None,
-                 max_batch: int = 1 << 14, oracle=None, device: int = 0, p_max: int = 64):
+                 max_batch: int = 1 << 14, oracle=None, device: int = 0, p_max: int = 64, native: bool = False):
         self.schedulerConfig = schedulerConfig
+        self.native = native
         self.mcs = mcs
         # (the payload areas of a DEMI_MODEL_PAYLOADS table's externals stay with the trace: `mcs` are its externals)
         self.ext_areas = trace.ext_areas if trace.ext_areas is not None and len(trace.ext_areas) == len(mcs) else None
@@ -431,6 +457,14 @@ class WildcardMinimizer:
         if own:
             self.oracle = StsWildcardOracle(self.schedulerConfig, device=self._device, p_max=self._p_max)
         try:
+            if self.native:
+                _, minTrace = self.oracle.minimize_native(self.mcs, self.trace, self.violation, self.clusteringStrategy,
+                                                          self.resolutionStrategy, skipClockClusters=self.skipClockClusters,
+                                                          stats=self._stats, max_batch=self.max_batch)
+                self.internal_sizes.extend(self.oracle.native_sizes)
+                self.batches.extend(self.oracle.native_batches)
+                self.speculative_replays += sum(self.oracle.native_batches)
+                return self._stats, minTrace
             if self.clusteringStrategy in (ClusteringStrategy.ClockClusterizer, ClusteringStrategy.ClockThenSingleton):
                 clusterizer = ClockClusterizer(self.trace, model, self.resolutionStrategy, aggressiveness=aggressiveness,
                                                skipClockClusters=self.skipClockClusters)

@@ -360,10 +360,11 @@ const char* demi_last_error(const demi_ctx* ctx);
 const char* demi_version(void);
 /* The layout generation of this header's structs.  It changes whenever a struct a caller fills or reads changes size or
  * meaning (4: demi_rec_event is 16 bytes with 16-bit payloads; demi_limits ends with executions_per_instance; demi_dpor_search
- * ends with ordering / max_distance_plus1 / resume; demi_dpor_stats ends with backtrack_points).  A binding built against
+ * ends with ordering / max_distance_plus1 / resume; demi_dpor_stats ends with backtrack_points; 5: demi_replay_wildcard_round and
+ * demi_minimize_wildcards with their structs).  A binding built against
  * another generation must refuse to run: compare demi_abi_version() with the DEMI_ABI_VERSION it was compiled with right
  * after loading the library (jni/demi_jni.c does so in JNI_OnLoad, demi_amd/_native.py in lib()). */
-#define DEMI_ABI_VERSION 4u
+#define DEMI_ABI_VERSION 5u
 uint32_t demi_abi_version(void);
 
 /* SchedulerConfig (SchedulerConfig.scala:9-37) + the application actors lowered to a table. */
@@ -611,6 +612,85 @@ int demi_replay_wildcard_candidates(demi_ctx* ctx, const uint64_t* masks /* [n_c
                                     const uint64_t* base_present /* [words] or NULL */, const uint32_t* drops /* [n_drop] */,
                                     uint32_t n_drop, const demi_limits* limits, demi_wildcard_candidate* out /* [n_cand] */,
                                     demi_verdict* out_all /* [n_cand * (1 + n_drop)] or NULL */);
+/* One ROUND of WildcardMinimizer.doMinimize (WildcardMinimizer.scala:182-240 around RunnerUtils.testWithStsSched): the wildcard
+ * counterpart of demi_replay_removal_round.  present[0..n) are the Clusterizer's upcoming proposals - each assuming the one before
+ * it failed - as presence rows of demi_replay_wildcard_batch over the loaded execution and selectors; ONE launch replays them,
+ * writes every proposal's executed-trace marks, counts its executed length, and reduces them ON THE DEVICE to what the sequential
+ * loop needs.  It replaces demi_replay_wildcard_batch, the host's search through n verdicts and the second, recording replay of
+ * the winner (demi_replay_wildcard_get_trace); the host reads one record and one row of marks.
+ *   mask          [4] or NULL: ONE subsequence of the externals for all proposals (NULL keeps every external);
+ *   first_hit     the lowest i for which demi_replay_wildcard_batch reports DEMI_V_VIOLATION and no capacity flag, 0xFFFFFFFF =
+ *                 none (also for n = 0);
+ *   verdict / out_kept [demi_replay_recorded_len]: byte for byte what demi_replay_wildcard_get_trace(mask, present[first_hit])
+ *                 returns (verdict all zero and out_kept untouched without a hit);  n_kept = marks set in out_kept;
+ *   executed_len  that call's *n_out: LENGTH CONVENTION of demi_wildcard_candidate.executed_len.
+ * Capacities as demi_replay_removal_round defines them: a proposal whose replay is aborted on a capacity BEFORE the first hit -
+ * anywhere when there is no hit - is no answer: the proposals up to the hit are evaluated again with p_max = DEMI_MAX_PENDING
+ * (`retried` counts them), and DEMI_ERR_CAPACITY is returned if an abort remains - never "does not reproduce".  An abort after the
+ * first hit is ignored: the sequential loop never gets there.  (The Python mirror's test_batch evaluates EVERY aborted candidate of
+ * a batch again, also those after the hit; the two differ only where Python raises.)
+ * A round whose marks (n x lowered events bytes) exceed the removal round's budget (64 MiB, the same experiment knob
+ * DEMI_INTMIN_KEPT_BYTES) runs as consecutive launches in proposal order and stops at the first launch that holds a hit.
+ * `launches` counts replay launches.  At most DEMI_MAX_REC_EVENTS proposals per call; the LIMITS of the wildcard replays apply. */
+typedef struct {
+  uint32_t first_hit;
+  uint32_t executed_len;
+  uint32_t n_kept;
+  uint32_t retried;
+  uint32_t launches;
+  uint32_t reserved;
+  demi_verdict verdict;
+} demi_wildcard_round_result;   /* 40 bytes */
+int demi_replay_wildcard_round(demi_ctx* ctx, const uint64_t* mask /* [4] or NULL */, const uint64_t* present /* [n][words] */,
+                               uint32_t n, const demi_limits* limits, uint8_t* out_kept /* [n_rec] */,
+                               demi_wildcard_round_result* result);
+
+/* ---------------------------------------------------------- wildcard minimization in one call
+ * Replaces WildcardMinimizer.minimize (minification/wildcard_minimization/WildcardMinimizer.scala:44-242) with
+ * TestScheduler.STSSched, over the execution loaded by demi_replay_load: the MCS as its externals, every external kept.  The
+ * Clusterizers (ClockClusterizer.scala with its ClockClusterIterator / OneAtATimeIterator and the three Aggressiveness levels,
+ * OneAtATimeClusterizer.scala) and the loop are csrc/wcmin_host.hpp, the same walk as demi_amd/wildcard_minimization.py.  The call
+ * lowers its own selectors (the caller does NOT call demi_replay_wildcard_load): a delivery of one of the table's external
+ * messages (msg_class DEMI_MSG_EXTERNAL) stays exact, a timer (clock_increment_types) becomes the timer wildcard, which bypasses
+ * the resolution strategy, every other delivery its class tag resolved by `policy`.  Per round up to max_batch upcoming proposals
+ * are enumerated on a copy of the Clusterizer and evaluated by demi_replay_wildcard_round; the Clusterizer is then advanced by the
+ * calls the sequential loop would have made, so the result, total_replays and the record_internal_size sequence are the
+ * sequential algorithm's.  Per adoption the loop needs only the winner's marks and executed length; the adopted TRACE is fetched
+ * once per doMinimize (one demi_replay_wildcard_get_trace of the last row that satisfied `ret.size <= minTrace.size`, :217), and
+ * reloaded, with the same externals, for the Singleton pass of DEMI_CLUSTER_CLOCK_THEN_SINGLETON.
+ *   out_trace [cap]: the minimized execution, *out_n its length;
+ *   out_sizes [sizes_cap] (may be NULL): record_internal_size after every sequential replay and the fencepost entry
+ *             (`sizes` entries; none with skip_clock_clusters);
+ *   out_batches [batches_cap] (may be NULL): proposals per round (`rounds` entries).
+ * THE LOADED EXECUTION CHANGES: on return the context holds the minimized execution and no selectors, as if the caller had called
+ * demi_replay_load(externals, out_trace) - also when an error is returned after the loop began (a replay that does not fit, an
+ * out_trace that is too small: the message names the length needed): then the last adopted trace is loaded.
+ * Refused by name (DEMI_ERR_INVALID_ARG): a table of more than 8 actors; limits->filter_known_absents != 0; an attached
+ * communicator ("single rank": rounds are not sharded); an unknown clustering or policy. */
+typedef enum { DEMI_CLUSTER_CLOCK = 0, DEMI_CLUSTER_SINGLETON = 1, DEMI_CLUSTER_CLOCK_THEN_SINGLETON = 2 } demi_clustering;
+typedef struct {
+  uint32_t clustering;                /* demi_clustering */
+  uint32_t policy;                    /* demi_wildcard_policy of the resolution strategy */
+  uint32_t skip_clock_clusters;       /* skipClockClusters: Aggressiveness.STOP_IMMEDIATELY, timers only */
+  uint32_t max_batch;                 /* proposals per round: 0 = 16384; 1 = the reference's one-replay-at-a-time loop */
+  uint32_t clock_increment_types;     /* bit t: MessageFingerprinter.causesClockIncrement of message type t */
+  uint8_t  clock_field[DEMI_MAX_MSG_TYPES];  /* getLogicalClock = DEMI_REC_PAYLOAD(e, n, clock_field[type]); 255 = none */
+} demi_wcmin_params;         /* 52 bytes */
+typedef struct {
+  uint64_t total_replays;    /* MinimizationStats.total_replays: the replays of the sequential loop */
+  uint64_t replays_run;      /* proposals replayed on the device, speculation, retries and the trace fetches included */
+  uint32_t rounds;           /* demi_replay_wildcard_round calls */
+  uint32_t launches;         /* replay launches: the rounds' (split or repeated ones included) and the trace fetches */
+  uint32_t adoptions;        /* proposals that still triggered the violation */
+  uint32_t retried;          /* proposals evaluated again with the largest pending set */
+  uint32_t sizes;            /* entries of the record_internal_size sequence */
+  uint32_t reserved;
+  uint32_t deliveries_before, deliveries_after;   /* countMsgEvents of the loaded / the minimized execution */
+} demi_wcmin_stats;          /* 48 bytes */
+int demi_minimize_wildcards(demi_ctx* ctx, const demi_limits* limits, const demi_wcmin_params* params,
+                            demi_rec_event* out_trace /* [cap] */, uint32_t cap, uint32_t* out_n,
+                            uint32_t* out_sizes /* [sizes_cap] or NULL */, uint32_t sizes_cap,
+                            uint32_t* out_batches /* [batches_cap] or NULL */, uint32_t batches_cap, demi_wcmin_stats* stats);
 /* external events of the trace demi_trace_load holds (0: none) - what demi_random_ddmin's `conjoined` array must cover */
 uint32_t demi_trace_len(const demi_ctx* ctx);
 

@@ -400,6 +400,70 @@ JNIEXPORT jint JNICALL FN(replayWildcardGetTrace)(JNIEnv* e, jclass c, jlong h, 
   SET_LONGS(verdict, 2, (const jlong*)(const void*)&v);
   return rc == DEMI_OK ? (jint)n_out : rc;
 }
+/* One round of WildcardMinimizer.doMinimize (demi_replay_wildcard_round) over the execution and selectors loaded.  present: long[words * n]
+ * (n proposals, each assuming the one before it failed); kept: byte[>= recorded events of the loaded execution]; result: long[8] =
+ * first_hit (-1: none), executed_len, n_kept, retried, launches, 0, then the winner's verdict as its two words */
+JNIEXPORT jint JNICALL FN(replayWildcardRound)(JNIEnv* e, jclass c, jlong h, jlongArray maskOrNull, jlongArray present, jint n, jintArray limits,
+                                              jbyteArray kept, jlongArray result) {
+  demi_limits lim;
+  demi_wildcard_round_result res;
+  (void)c;
+  if (limits_of(e, limits, &lim) || !present || n < 0 || LEN(present) < present_words(h) * (int64_t)n || LEN(kept) < 0 || LEN(result) != 8 ||
+      (maskOrNull && LEN(maskOrNull) != 4))
+    return DEMI_ERR_INVALID_ARG;
+  if ((uint64_t)LEN(kept) < (uint64_t)demi_replay_recorded_len(CTX(h))) return DEMI_ERR_CAPACITY;
+  memset(&res, 0, sizeof res);
+  void* m = LONGS(maskOrNull);
+  void* p = LONGS(present);
+  void* k = BYTES(kept);
+  jint rc = (LOST(maskOrNull, m) || LOST(present, p) || LOST(kept, k)) ? DEMI_ERR_INVALID_ARG
+            : demi_replay_wildcard_round(CTX(h), (const uint64_t*)m, (const uint64_t*)p, (uint32_t)n, &lim, (uint8_t*)k, &res);
+  PUT_BYTES(kept, k, 0);
+  PUT_LONGS(present, p, JNI_ABORT);
+  PUT_LONGS(maskOrNull, m, JNI_ABORT);
+  jlong r[8];
+  r[0] = (jlong)(int32_t)res.first_hit; r[1] = (jlong)res.executed_len; r[2] = (jlong)res.n_kept; r[3] = (jlong)res.retried;
+  r[4] = (jlong)res.launches; r[5] = 0;
+  memcpy(&r[6], &res.verdict, sizeof res.verdict);
+  SET_LONGS(result, 8, r);
+  return rc;
+}
+/* WildcardMinimizer.minimize in one call (demi_minimize_wildcards) on the execution replayLoad loaded; the loaded execution is the minimized
+ * one afterwards, without selectors.  params: int[5] = clustering (0 ClockClusterizer, 1 SingletonClusterizer, 2 ClockThenSingleton), policy
+ * (0 HEAD, 1 FIRST, 2 LAST), skip_clock_clusters, max_batch, clock_increment_types (bit t); clockField: byte[32] (payload field of the
+ * logical clock per message type, -1 = none); trace: byte[16 * cap] receives the minimized recorded events; sizesOrNull: int[] the
+ * record_internal_size sequence; stats: long[10] = events of the result, total_replays, replays_run, rounds, launches, adoptions, retried,
+ * entries of the sizes sequence, deliveries_before, deliveries_after */
+JNIEXPORT jint JNICALL FN(minimizeWildcards)(JNIEnv* e, jclass c, jlong h, jintArray limits, jintArray params, jbyteArray clockField,
+                                            jbyteArray trace, jintArray sizesOrNull, jlongArray stats) {
+  demi_limits lim;
+  demi_wcmin_params par;
+  demi_wcmin_stats st;
+  jint pr[5];
+  uint32_t n = 0;
+  (void)c;
+  if (limits_of(e, limits, &lim) || LEN(params) != 5 || LEN(clockField) != DEMI_MAX_MSG_TYPES || LEN(trace) < 0 || LEN(stats) != 10)
+    return DEMI_ERR_INVALID_ARG;
+  (*e)->GetIntArrayRegion(e, params, 0, 5, pr);
+  memset(&par, 0, sizeof par);
+  par.clustering = (uint32_t)pr[0]; par.policy = (uint32_t)pr[1]; par.skip_clock_clusters = (uint32_t)pr[2]; par.max_batch = (uint32_t)pr[3];
+  par.clock_increment_types = (uint32_t)pr[4];
+  (*e)->GetByteArrayRegion(e, clockField, 0, DEMI_MAX_MSG_TYPES, (jbyte*)par.clock_field);
+  memset(&st, 0, sizeof st);
+  void* t = BYTES(trace);
+  void* z = INTS(sizesOrNull);
+  jint rc = (LOST(trace, t) || LOST(sizesOrNull, z)) ? DEMI_ERR_INVALID_ARG
+            : demi_minimize_wildcards(CTX(h), &lim, &par, (demi_rec_event*)t, (uint32_t)(LEN(trace) / (jint)sizeof(demi_rec_event)), &n,
+                                      (uint32_t*)z, sizesOrNull ? (uint32_t)LEN(sizesOrNull) : 0u, NULL, 0, &st);
+  PUT_INTS(sizesOrNull, z, 0);
+  PUT_BYTES(trace, t, 0);
+  jlong o[10];
+  o[0] = (jlong)n; o[1] = (jlong)st.total_replays; o[2] = (jlong)st.replays_run; o[3] = (jlong)st.rounds; o[4] = (jlong)st.launches;
+  o[5] = (jlong)st.adoptions; o[6] = (jlong)st.retried; o[7] = (jlong)st.sizes; o[8] = (jlong)st.deliveries_before;
+  o[9] = (jlong)st.deliveries_after;
+  SET_LONGS(stats, 10, o);
+  return rc;
+}
 /* ---- WildcardTestOracle.test per candidate (demi_replay_wildcard_candidates).  masks: long[4 * n]; basePresentOrNull: long[words];
  *      drops: int[n_drop] (may be empty); out: long[3 * n] = demi_wildcard_candidate (first_hit | executed_len << 32, flags | first_ovf << 32,
  *      hash); outAllOrNull: long[2 * n * (1 + n_drop)] */

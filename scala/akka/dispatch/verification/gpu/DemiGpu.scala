@@ -104,6 +104,19 @@ object DemiGpu {
    *  `recorded` (16 bytes each), or a negative status; kept = byte[n recorded] */
   @native def replayWildcardGetTrace(h: Long, maskOrNull: Array[Long], present: Array[Long], limits: Array[Int], verdict: Array[Long],
                                      kept: Array[Byte], recorded: Array[Byte]): Int
+  /** one round of WildcardMinimizer.doMinimize, reduced on the device (demi_replay_wildcard_round): present = long[ceil(n recorded / 64) * n],
+   *  the clusterizer's n upcoming proposals; kept = byte[n recorded] (the executed-trace marks of proposal first_hit); result = long[8]
+   *  (first_hit or -1, executed_len, n_kept, retried, launches, 0, the winner's two verdict words) */
+  @native def replayWildcardRound(h: Long, maskOrNull: Array[Long], present: Array[Long], n: Int, limits: Array[Int], kept: Array[Byte],
+                                  result: Array[Long]): Int
+  /** WildcardMinimizer.minimize in one call (demi_minimize_wildcards) on the execution replayLoad loaded, which is the minimized one
+   *  afterwards (no selectors; the call lowers its own): params = int[5] (clustering: 0 ClockClusterizer, 1 SingletonClusterizer,
+   *  2 ClockThenSingleton; policy: 0 HEAD, 1 FIRST, 2 LAST; skipClockClusters; max_batch; clock-increment types, bit t), clockField =
+   *  byte[32] (payload field of getLogicalClock per message type, -1: none), trace = byte[16 * cap], sizesOrNull = int[]
+   *  (record_internal_size per replay and the fencepost), stats = long[10] (events of the result, total_replays, replays_run, rounds,
+   *  launches, adoptions, retried, entries of sizes, deliveries_before, deliveries_after) */
+  @native def minimizeWildcards(h: Long, limits: Array[Int], params: Array[Int], clockField: Array[Byte], trace: Array[Byte],
+                                sizesOrNull: Array[Int], stats: Array[Long]): Int
   /** one WildcardTestOracle.test per candidate (demi_replay_wildcard_candidates): masks = long[4 * n]; proposal 0 = basePresentOrNull
    *  (null: every delivery), proposal j = that row without the MsgEvent recorded at drops(j - 1); out = long[3 * n]
    *  (first_hit | executed_len << 32, flags | first_ovf << 32, hash; flags: 1 reproduces, 2 unknown because of a capacity, 4 longer than

@@ -564,6 +564,66 @@ object GpuWildcardDDMin {
   }
 }
 
+/** WildcardMinimizer.minimize (minification/wildcard_minimization/WildcardMinimizer.scala:44-242) with TestScheduler.STSSched in ONE call
+ *  of the library (demi_minimize_wildcards): the Clusterizers, the rounds of speculative proposals and the adoption of the first that
+ *  reproduces run natively; per round the host reads one record and one row of marks.  `mcs` are the externals every replay keeps.
+ *  clusteringStrategy: 0 ClockClusterizer, 1 SingletonClusterizer, 2 ClockThenSingleton.  The clock hooks are the fingerprinter's:
+ *  causesClockIncrement over the trace's deliveries gives the timer types, getLogicalClock the payload field that carries the clock
+ *  (lowering.clockField where the lowering states it; else the field whose encoded value equals the clock in every delivery of the
+ *  type).  Returns (stats, the minimized trace, the record_internal_size sequence). */
+object GpuWildcardMinimizer {
+  def apply(schedulerConfig: SchedulerConfig, lowering: TableLowering, mcs: Seq[ExternalEvent], trace: EventTrace,
+            violation: ViolationFingerprint, skipClockClusters: Boolean = false, resolutionStrategy: AmbiguityResolutionStrategy = null,
+            clusteringStrategy: Int = 0, stats: Option[MinimizationStats] = None, device: Int = 0, pMax: Int = 64,
+            maxBatch: Int = 0): (MinimizationStats, EventTrace, Array[Int]) = {
+    if (schedulerConfig.invariant_check.isEmpty) throw new IllegalArgumentException("Must invoke setInvariant before test()")
+    if (schedulerConfig.filterKnownAbsents) throw new UnsupportedOnGpu("the wildcard replay with filterKnownAbsents")
+    val h = ctxCreate(device)
+    if (h == 0) throw new IllegalStateException("no MI355X visible: use WildcardMinimizer")
+    try {
+      val m = lowering.model
+      check(h, modelLoad(h, m.nActors, m.msgClass, m.actorClass, m.nClasses, m.handlerStart, m.code, m.initState,
+                         Array(m.invKind, m.invFa, m.invVa, m.invFb, m.fpMatchMask, m.flags)))
+      if (m.compiledOnly) check(h, modelSpecialize(h, true)) else modelSpecialize(h, true)
+      val packed = FlatEvents.packRecorded(trace, lowering)
+      check(h, replayLoad(h, FlatEvents.pack(mcs, lowering), packed))
+      val fingerprinter = schedulerConfig.messageFingerprinter
+      val policy = resolutionStrategy match {
+        case _: SrcDstFIFOOnly => 0
+        case _: LastOnlyStrategy => 2
+        case _ => 1
+      }
+      var incTypes = 0
+      val clockField = Array.fill[Byte](32)(-1)
+      val candidates = scala.collection.mutable.Map[Int, Set[Int]]()                // message type -> fields that equalled the clock so far
+      for (e <- trace.events) e match {
+        case UniqueMsgEvent(MsgEvent(_, _, msg), _) if !EventTypes.isExternal(e) =>
+          val (t, fields) = lowering.encodeFields(msg)
+          if (fingerprinter.causesClockIncrement(msg)) incTypes |= 1 << t
+          fingerprinter.getLogicalClock(msg) match {
+            case Some(clock) if lowering.clockField(t) < 0 =>
+              val equal = fields.indices.filter(k => fields(k).toLong == clock).toSet
+              candidates(t) = candidates.get(t).map(_ & equal).getOrElse(equal)
+            case Some(_) => clockField(t) = lowering.clockField(t).toByte
+            case None =>
+          }
+        case _ =>
+      }
+      for ((t, ks) <- candidates) {
+        if (ks.isEmpty) throw new UnsupportedOnGpu("getLogicalClock of message type " + t + " is none of its encoded fields")
+        clockField(t) = ks.min.toByte
+      }
+      val limits = Array(0, 0, pMax, 1, lowering.fingerprintCode(violation), 0, 0, 0, 1)
+      val out = new Array[Byte](16 * MAX_REC_EVENTS); val sizes = new Array[Int](2 * MAX_REC_EVENTS + 4); val st = new Array[Long](10)
+      check(h, DemiGpu.minimizeWildcards(h, limits, Array(clusteringStrategy, policy, if (skipClockClusters) 1 else 0, maxBatch, incTypes),
+                                         clockField, out, sizes, st))
+      val s = stats.getOrElse(new MinimizationStats)
+      (0L until st(1)).foreach(_ => s.increment_replays())
+      (s, FlatEvents.toEventTrace(out, st(0).toInt, mcs, lowering), sizes.take(math.min(st(7).toInt, sizes.length)))
+    } finally ctxDestroy(h)
+  }
+}
+
 object GpuDPOR {
   /** demi_dpor_trace_entry[] (key 8, word 4, parent, qperiod, depth, kind) -> the MsgEvents of the violating interleaving */
   def traceOf(vt: Array[Byte], n: Int, externals: Seq[ExternalEvent], lo: TableLowering): EventTrace = {

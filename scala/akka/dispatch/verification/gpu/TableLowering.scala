@@ -51,6 +51,9 @@ trait TableLowering {
   /** Messages with more than two fields (model.payloads > 2): every field, P0 first.  The defaults serve two-field tables. */
   def encodeFields(msg: Any): (Int, Seq[Int]) = { val (t, p0, p1) = encode(msg); (t, Seq(p0, p1)) }
   def decodeFields(msgType: Int, fields: Seq[Int]): Any = decode(msgType, fields(0), fields(1))
+  // which payload field of message type t carries MessageFingerprinter.getLogicalClock, 255 = none: what ClockClusterizer clusters
+  // by (GpuWildcardMinimizer).  -1 = not stated: the field is found by comparing getLogicalClock with the encoded fields.
+  def clockField(msgType: Int): Int = -1
   def fingerprintCode(fp: ViolationFingerprint): Int  // 32-bit code of demi_verdict.fingerprint
   def fingerprintOf(code: Int): ViolationFingerprint
 }

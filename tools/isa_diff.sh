@@ -29,6 +29,7 @@ root, out = sys.argv[1], sys.argv[2]
 sys.path.insert(0, root); os.chdir(root)
 os.environ["DEMI_JIT_DUMP"] = out
 os.environ["DEMI_SPECIALIZE_CHECK_TESTS"] = "1"     # (the workgroup-per-test modules too, where the tree has them)
+os.environ["DEMI_SPECIALIZE_CHECK_ROUND"] = "1"     # (and the wildcard round's module)
 from demi_amd import _native, model as M
 assert _native.__file__.startswith(root)
 _native.specialize_check(M.raft_model(5).to_struct())
