@@ -216,6 +216,57 @@ __device__ __forceinline__ uint32_t tq_rcv(uint32_t b) { return b >> 5; }
 __device__ __forceinline__ uint32_t tq_type(uint32_t b) { return b & 31u; }
 #endif
 
+// K1's two timer queues behind one type: push, concatenate, remove-first-equal, iterate (the counts stay with the caller: they
+// are compared against DEMI_TQ_CAP / DEMI_RESEND_CAP there, and both capacities are at most 8 entries in either form).
+// The byte form is the entry of tq_pack above in a 64-bit word.  The 4-bit form - a K1 compiled for a small-layout table with
+// n_actors * n_timer_types <= 16 (jit.hpp tq_defines: DEMI_JIT_TQ4_TYPES = the message type of timer index k in bits
+// 5k .. 5k + 4) - names an entry by its timer-directory index rcv * NTT + timer index: eight of them are one 32-bit register,
+// and every shift, OR and the zero-entry search of the cancel path is a full-rate 32-bit operation.
+// (DEMI_K1_TQ_BYTES: the byte form in such a build too, for A/B runs)
+#if defined(DEMI_JIT_TQ4_TYPES) && !defined(DEMI_BIG) && !defined(DEMI_K1_TQ_BYTES)
+constexpr bool TQ_NARROW = true;
+struct TimerQ {
+  typedef uint32_t bits_t;
+  static constexpr uint32_t W = 4;
+  static constexpr bits_t ONES = 0x11111111u;
+  bits_t bits;
+  static __device__ __forceinline__ uint32_t pack(uint32_t rcv, uint32_t type, uint32_t tix) { (void)type; return rcv * (DEMI_JIT_NTT) + tix; }
+  static __device__ __forceinline__ uint32_t rcv_of(uint32_t e) { return e / (DEMI_JIT_NTT); }
+  static __device__ __forceinline__ uint32_t type_of(uint32_t e) { return ((uint32_t)(DEMI_JIT_TQ4_TYPES) >> (5u * (e % (DEMI_JIT_NTT)))) & 31u; }
+  static __device__ __forceinline__ bits_t splat(uint32_t e) { bits_t r = e | (e << 4); r |= r << 8; return r | (r << 16); }
+#else
+constexpr bool TQ_NARROW = false;
+struct TimerQ {
+  typedef uint64_t bits_t;
+  static constexpr uint32_t W = 8;
+  static constexpr bits_t ONES = 0x0101010101010101ull;
+  bits_t bits;
+  static __device__ __forceinline__ uint32_t pack(uint32_t rcv, uint32_t type, uint32_t tix) { return tq_pack(rcv, type, tix); }
+  static __device__ __forceinline__ uint32_t rcv_of(uint32_t e) { return tq_rcv(e); }
+  static __device__ __forceinline__ uint32_t type_of(uint32_t e) { return tq_type(e); }
+  static __device__ __forceinline__ bits_t splat(uint32_t e) { return ONES * (bits_t)e; }
+#endif
+  static constexpr uint32_t CAP = 8 * sizeof(bits_t) / W;      // entries of a word
+  __device__ __forceinline__ void clear() { bits = 0; }
+  // entry e behind the n < CAP entries held
+  __device__ __forceinline__ void push(uint32_t n, uint32_t e) { bits |= (bits_t)e << (W * n); }
+  // the entries of `o` behind the n held (the caller has checked that they fit; o is not empty, so n < CAP)
+  __device__ __forceinline__ void append(uint32_t n, const TimerQ& o) { bits |= o.bits << (W * n); }
+  __device__ __forceinline__ uint32_t at(uint32_t k) const { return (uint32_t)(bits >> (W * k)) & ((1u << W) - 1u); }
+  // removes the first of the n entries equal to e, if any: all compared at once (zero-entry test on bits ^ e...e; its lowest
+  // hit is exact), the entries behind it move down
+  __device__ __forceinline__ bool remove_first(uint32_t n, uint32_t e) {
+    const bits_t x = bits ^ splat(e);
+    bits_t z = (x - ONES) & ~x & (ONES << (W - 1));
+    z &= (n >= CAP) ? ~(bits_t)0 : (((bits_t)1 << (W * n)) - (bits_t)1);
+    if (z == 0) return false;
+    const uint32_t q = (uint32_t)(sizeof(bits_t) == 8 ? __builtin_ctzll(z) : __builtin_ctz((uint32_t)z)) / W;
+    const bits_t lowm = ((bits_t)1 << (W * q)) - (bits_t)1;
+    bits = (bits & lowm) | ((bits >> W) & ~lowm);
+    return true;
+  }
+};
+
 __device__ __forceinline__ void hash_step(uint64_t& h, uint64_t v) { h = (h ^ v) * 0x100000001B3ULL; }
 
 // ------------------------------------------------------------------ invariant

@@ -226,6 +226,21 @@ inline uint32_t k1_fxq_slots(const demi::DevModel& h, bool sched) {
   return nq ? nq : 1u;
 }
 
+// ------------------------------------------------------------------ K1's timer queues (demi_device.hpp TimerQ)
+// The 4-bit form names a queued timer by its timer-directory index rcv * n_timer_types + timer index: valid for a small-layout
+// table whose directory has at most 16 entries.  What the kernel then needs back from an entry is its message type, so the
+// table's timer index -> message type map goes along as a constant (type of index k in bits 5k .. 5k + 4).  Every other table
+// gets no line and keeps the byte form.
+inline std::string tq_defines(const demi::DevModel& h) {
+  if (h.n_actors > DEMI_MAX_ACTORS || h.n_timer_types == 0 || h.n_actors * h.n_timer_types > 16) return "";
+  uint32_t type_of_tix = 0;
+  for (uint32_t t = 0; t < h.n_msg_types; t++)
+    if ((h.timer_types >> t) & 1u) type_of_tix |= t << (5u * ((h.meta[t] >> 8) & 3u));
+  char buf[64];
+  snprintf(buf, sizeof buf, "#define DEMI_JIT_TQ4_TYPES 0x%xu\n", type_of_tix);
+  return buf;
+}
+
 // ------------------------------------------------------------------ code generation
 // One statement block per row; forward skips become gotos (the table has no backward edges, validation
 // guarantees it), handler entry is a switch over the distinct handler starts.

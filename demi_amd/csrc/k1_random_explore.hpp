@@ -504,9 +504,21 @@ __global__ K1_LAUNCH_BOUNDS void k1_random_explore(const typename K1ArgsOf<V>::t
   Net net;
   net.inaccessible = 0; net.killed = 0; pairs_clear(net.partitioned);
   uint64_t reach = 0;                 // !REC: the batch's reach matrix (K1_BATCH_WORDS above; BIG: read from the batch table instead)
-  uint64_t tq = 0, resend = 0;        // messagesToSend timers / timersToResend: 1 byte each (demi_device.hpp tq_pack)
+  TimerQ tq = {0}, resend = {0};      // messagesToSend timers / timersToResend (demi_device.hpp TimerQ)
   uint32_t n_tq = 0, n_resend = 0;
   tmask_t just = 0, rep = 0;          // justScheduledTimers / registered repeating timers (bit rcv*4+tidx)
+  // The timers that MAY have an entry in tq (same bits): set by every enqueue into tq, cleared when the flush empties it, never
+  // cleared by a removal - a superset.  A cancel searches tq only for a timer in it: tq is non-empty during most apply phases
+  // because the previous heartbeat's resend list re-entered it, which are entries of OTHER timers than the one being cancelled,
+  // and with 50 lanes delivering some lane has n_tq != 0 in almost every iteration.  The search stays the authority.
+  // (DEMI_K1_NO_INQ: search whenever tq is not empty, for A/B runs.  REBIN does that too: the mask is not among the words its
+  // lanes exchange.)
+  tmask_t inq = 0;
+#ifdef DEMI_K1_NO_INQ
+  constexpr bool INQ = false;
+#else
+  constexpr bool INQ = !REBIN;
+#endif
   // the created actors a message sent by `snd` reaches under the current batch's network state
   auto reach_row = [&](uint32_t snd) -> uint32_t {
 #ifdef DEMI_BIG
@@ -605,15 +617,16 @@ __global__ K1_LAUNCH_BOUNDS void k1_random_explore(const typename K1ArgsOf<V>::t
 
   // RandomScheduler.enqueue_timer (:549-559) -> handle_timer (ExternalEventInjector.scala:282-297)
   auto enqueue_timer = [&](uint32_t rcv, uint32_t type, tmask_t tbit) {      // tbit = TIMER_BIT(rcv, type)
-    const uint64_t b = (uint64_t)tq_pack(rcv, type, BIG_TU ? tix_of(type) : 0u);
+    const uint32_t b = TimerQ::pack(rcv, type, (BIG_TU || TQ_NARROW) ? tix_of(type) : 0u);
     if (just & tbit) {
       if (n_resend >= DEMI_RESEND_CAP) { flags |= DEMI_V_QUEUE_OVF; return; }
-      resend |= b << (8 * n_resend);
+      resend.push(n_resend, b);
       n_resend++;
     } else {
       if (n_tq >= DEMI_TQ_CAP) { flags |= DEMI_V_QUEUE_OVF; return; }
-      tq |= b << (8 * n_tq);
+      tq.push(n_tq, b);
       n_tq++;
+      if (INQ) inq |= tbit;
     }
   };
 
@@ -724,7 +737,7 @@ __global__ K1_LAUNCH_BOUNDS void k1_random_explore(const typename K1ArgsOf<V>::t
           ph = PH_INJECT; fresh = true;
         }
         n_pend = 0; count = 0; cnt_mod = 0; tidx = 0; inj_lo = 0; inj_hi = 0; batch_no = 0;
-        tq = 0; resend = 0; n_tq = 0; n_resend = 0; just = 0; rep = 0; viol = 0; flags = 0; hash = 0;
+        tq.clear(); resend.clear(); n_tq = 0; n_resend = 0; just = 0; rep = 0; inq = 0; viol = 0; flags = 0; hash = 0;
         n_norm = 0; n_pairs = 0; pairmask = 0;
       }
       PH_MARK(10);
@@ -917,13 +930,14 @@ __global__ K1_LAUNCH_BOUNDS void k1_random_explore(const typename K1ArgsOf<V>::t
       // ... then timers: internal messages from deadLetters, dropped when the receiver is
       // inaccessible (crosses_partition(deadLetters, rcv), :287-297)
       for (uint32_t k = 0; k < n_tq; k++) {
-        const uint32_t bt = (uint32_t)(tq >> (8 * k)) & 0xFF, rcv = tq_rcv(bt), type = tq_type(bt);
+        const uint32_t bt = tq.at(k), rcv = TimerQ::rcv_of(bt), type = TimerQ::type_of(bt);
         const uint32_t id = next_id; if (REC) next_id++;
         const bool drop = (net.inaccessible >> rcv) & 1;
-        if (!drop) PEND_APPEND(msg_word(type, DL, rcv, 0, 0), id, (int32_t)(rcv * NTT + tix_of(type)));
+        // (the 4-bit entry IS the timer's directory index)
+        if (!drop) PEND_APPEND(msg_word(type, DL, rcv, 0, 0), id, (int32_t)(TQ_NARROW ? bt : rcv * NTT + tix_of(type)));
         REC_PUSH(DEMI_REC_MSG_SEND, DL, rcv, type, 0, 2 | (drop ? 4 : 0), 255, id);
       }
-      tq = 0; n_tq = 0;
+      tq.clear(); n_tq = 0; inq = 0;
       if ((flags & DEMI_OVF_ANY) || n_pend + n_norm == 0) none = true;
     }
     PH_MARK(3);
@@ -1054,9 +1068,9 @@ __global__ K1_LAUNCH_BOUNDS void k1_random_explore(const typename K1ArgsOf<V>::t
           // timersToResend re-enter messagesToSend in order (RandomScheduler.scala:416-419): one shifted OR
           if (n_resend != 0) {
             if (n_tq + n_resend > DEMI_TQ_CAP) flags |= DEMI_V_QUEUE_OVF;
-            else { tq |= resend << (8 * n_tq); n_tq += n_resend; }
+            else { tq.append(n_tq, resend); n_tq += n_resend; if (INQ) inq |= just; }     // (every member of resend has its bit in `just`)
           }
-          resend = 0; n_resend = 0; just = 0;
+          resend.clear(); n_resend = 0; just = 0;
         }
         deliver = !(flags & DEMI_OVF_ANY);
         if (!deliver) ph = PH_FINISH;
@@ -1085,8 +1099,8 @@ __global__ K1_LAUNCH_BOUNDS void k1_random_explore(const typename K1ArgsOf<V>::t
         const uint32_t me_ = w_dst(w);
         xo[k++ * RB_WG] = (flags & 0xFu) | (n_pend << 4) | (n_tq << 12) | (n_resend << 16) | (((uint32_t)(reach >> (me_ * 8)) & 0xFFu) << 20);
         xo[k++ * RB_WG] = (uint32_t)lastw; if (WIDE_TU) xo[k++ * RB_WG] = (uint32_t)((uint64_t)lastw >> 32);
-        xo[k++ * RB_WG] = (uint32_t)tq; xo[k++ * RB_WG] = (uint32_t)(tq >> 32);
-        xo[k++ * RB_WG] = (uint32_t)resend; xo[k++ * RB_WG] = (uint32_t)(resend >> 32);
+        xo[k++ * RB_WG] = (uint32_t)tq.bits; xo[k++ * RB_WG] = (uint32_t)((uint64_t)tq.bits >> 32);
+        xo[k++ * RB_WG] = (uint32_t)resend.bits; xo[k++ * RB_WG] = (uint32_t)((uint64_t)resend.bits >> 32);
         xo[k++ * RB_WG] = just; xo[k++ * RB_WG] = rep;
         if (RB_CRASHES) xo[k++ * RB_WG] = blocked;
         if (APP_RND) { xo[k++ * RB_WG] = (uint32_t)app_rng; xo[k++ * RB_WG] = (uint32_t)(app_rng >> 32); }
@@ -1132,8 +1146,8 @@ __global__ K1_LAUNCH_BOUNDS void k1_random_explore(const typename K1ArgsOf<V>::t
         const uint32_t pk = xi[j++ * RB_WG];
         flags = pk & 0xFu; n_pend = (pk >> 4) & 0xFFu; n_tq = (pk >> 12) & 0xFu; n_resend = (pk >> 16) & 0xFu;
         { uint64_t lw = xi[j++ * RB_WG]; if (WIDE_TU) lw |= (uint64_t)xi[j++ * RB_WG] << 32; lastw = (word_t)lw; }
-        tq = xi[j * RB_WG] | ((uint64_t)xi[(j + 1) * RB_WG] << 32); j += 2;
-        resend = xi[j * RB_WG] | ((uint64_t)xi[(j + 1) * RB_WG] << 32); j += 2;
+        tq.bits = (TimerQ::bits_t)(xi[j * RB_WG] | ((uint64_t)xi[(j + 1) * RB_WG] << 32)); j += 2;
+        resend.bits = (TimerQ::bits_t)(xi[j * RB_WG] | ((uint64_t)xi[(j + 1) * RB_WG] << 32)); j += 2;
         just = xi[j++ * RB_WG]; rep = xi[j++ * RB_WG];
         if (RB_CRASHES) blocked = xi[j++ * RB_WG];
         if (APP_RND) { app_rng = xi[j * RB_WG] | ((uint64_t)xi[(j + 1) * RB_WG] << 32); j += 2; }
@@ -1198,20 +1212,11 @@ __global__ K1_LAUNCH_BOUNDS void k1_random_explore(const typename K1ArgsOf<V>::t
     // cancelTimer (Instrumenter.scala:159-168) -> notify_timer_cancel (:525-534)
     auto apply_cancel = [&](uint32_t type, tmask_t tbit, uint32_t tix) {      // tbit = TIMER_BIT(me, type), tix = its timer index
       rep &= ~tbit;
-      const uint32_t want = tq_pack(me, type, tix);
-      // handle_timer_cancel: messagesToSend first.  The first of its n_tq bytes equal to `want`, all eight
-      // compared at once (zero-byte test on tq ^ want...want; its lowest hit is exact)
+      // handle_timer_cancel: messagesToSend first - the first of its n_tq entries for this timer (TimerQ::remove_first), looked
+      // for only when the timer may be there (`inq` above)
       bool found = false;
-      if (n_tq != 0) {
-        const uint64_t x = tq ^ (0x0101010101010101ull * (uint64_t)want);
-        uint64_t z = (x - 0x0101010101010101ull) & ~x & 0x8080808080808080ull;
-        z &= (n_tq >= 8) ? ~0ull : ((1ull << (8 * n_tq)) - 1ull);
-        if (z != 0) {
-          const uint32_t q = (uint32_t)__builtin_ctzll(z) >> 3;
-          const uint64_t lowm = (1ull << (8 * q)) - 1ull;
-          tq = (tq & lowm) | ((tq >> 8) & ~lowm);
-          n_tq--; found = true;
-        }
+      if (INQ ? (inq & tbit) != 0 : n_tq != 0) {
+        if (tq.remove_first(n_tq, TimerQ::pack(me, type, tix))) { n_tq--; found = true; }
       }
       if (!found) {
         // FullyRandom.remove (:653-664): first match in arr order, then swap-remove.  The timer directory knows the slot
@@ -1286,8 +1291,8 @@ __global__ K1_LAUNCH_BOUNDS void k1_random_explore(const typename K1ArgsOf<V>::t
         uint32_t k = 0;
         xb[k++ * RB_WG] = (flags & 0xFu) | (n_pend << 4) | (n_tq << 12) | (n_resend << 16) | (rb_hit << 28);
         xb[k++ * RB_WG] = (uint32_t)lastw; if (WIDE_TU) xb[k++ * RB_WG] = (uint32_t)((uint64_t)lastw >> 32);
-        xb[k++ * RB_WG] = (uint32_t)tq; xb[k++ * RB_WG] = (uint32_t)(tq >> 32);
-        xb[k++ * RB_WG] = (uint32_t)resend; xb[k++ * RB_WG] = (uint32_t)(resend >> 32);
+        xb[k++ * RB_WG] = (uint32_t)tq.bits; xb[k++ * RB_WG] = (uint32_t)((uint64_t)tq.bits >> 32);
+        xb[k++ * RB_WG] = (uint32_t)resend.bits; xb[k++ * RB_WG] = (uint32_t)((uint64_t)resend.bits >> 32);
         xb[k++ * RB_WG] = just; xb[k++ * RB_WG] = rep;
         if (RB_CRASHES) xb[k++ * RB_WG] = blocked;
         if (APP_RND) { xb[k++ * RB_WG] = (uint32_t)app_rng; xb[k++ * RB_WG] = (uint32_t)(app_rng >> 32); }
@@ -1299,8 +1304,8 @@ __global__ K1_LAUNCH_BOUNDS void k1_random_explore(const typename K1ArgsOf<V>::t
         const uint32_t pk = xi[j++ * RB_WG];
         flags = pk & 0xFu; n_pend = (pk >> 4) & 0xFFu; n_tq = (pk >> 12) & 0xFu; n_resend = (pk >> 16) & 0xFu;
         { uint64_t lw = xi[j++ * RB_WG]; if (WIDE_TU) lw |= (uint64_t)xi[j++ * RB_WG] << 32; lastw = (word_t)lw; }
-        tq = xi[j * RB_WG] | ((uint64_t)xi[(j + 1) * RB_WG] << 32); j += 2;
-        resend = xi[j * RB_WG] | ((uint64_t)xi[(j + 1) * RB_WG] << 32); j += 2;
+        tq.bits = (TimerQ::bits_t)(xi[j * RB_WG] | ((uint64_t)xi[(j + 1) * RB_WG] << 32)); j += 2;
+        resend.bits = (TimerQ::bits_t)(xi[j * RB_WG] | ((uint64_t)xi[(j + 1) * RB_WG] << 32)); j += 2;
         just = xi[j++ * RB_WG]; rep = xi[j++ * RB_WG];
         if (RB_CRASHES) blocked = xi[j++ * RB_WG];
         if (APP_RND) { app_rng = xi[j * RB_WG] | ((uint64_t)xi[(j + 1) * RB_WG] << 32); j += 2; }
