@@ -22,7 +22,8 @@ EXPORTS = ["demi_ctx_create", "demi_ctx_destroy", "demi_last_error", "demi_versi
            "demi_replay_wildcard_candidates", "demi_wildcard_ddmin",
            "demi_fuzz_stride", "demi_fuzz_generate", "demi_random_explore_tests", "demi_fuzz_campaign",
            "demi_fuzz_generate_fields", "demi_random_explore_tests_areas", "demi_fuzz_campaign_fields",
-           "demi_replay_removal_round", "demi_minimize_internals", "demi_replay_wildcard_round", "demi_minimize_wildcards"]
+           "demi_replay_removal_round", "demi_minimize_internals", "demi_replay_wildcard_round", "demi_minimize_wildcards",
+           "demi_replay_batch_submit", "demi_replay_batch_wait"]
 
 _lib = None
 ALLGATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t)     # demi_allgather_fn
@@ -129,6 +130,9 @@ def lib():
     L.demi_random_explore_submit.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(T.Limits), C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32)]
     L.demi_random_explore_wait.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint64),
                                            C.POINTER(C.c_uint64)]
+    L.demi_replay_batch_submit.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(T.Limits), C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32)]
+    L.demi_replay_batch_wait.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint64),
+                                         C.POINTER(C.c_uint64)]
     L.demi_collect_flagged_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint32,
                                            C.c_void_p, C.c_void_p]
     L.demi_comm_unique_id.argtypes = [C.c_void_p]
@@ -321,6 +325,27 @@ class Context:
         self._check(lib().demi_replay_batch(self._h, masks.ctypes.data if len(masks) else None, len(masks),
                                             C.byref(limits), out.ctypes.data if len(masks) else None))
         return out
+
+    def replay_batch_submit(self, masks, limits, flag_mask=0, want_verdicts=False):
+        """replay_batch() in pieces, up to three outstanding: enqueue the candidates `masks` (uint64[n, 4]; copied before this returns)
+        on a stream of the context's own; returns the ticket.  want_verdicts: every verdict travels to the library's pinned memory
+        behind the call (replay_batch_wait(out=...))."""
+        import numpy as np
+        masks = np.ascontiguousarray(masks, dtype=np.uint64).reshape(-1, 4)
+        t = C.c_uint32(0)
+        self._check(lib().demi_replay_batch_submit(self._h, masks.ctypes.data if len(masks) else None, len(masks), C.byref(limits),
+                                                   flag_mask, 1 if want_verdicts else 0, C.byref(t)))
+        return int(t.value)
+
+    def replay_batch_wait(self, ticket, out=None, cap=1 << 16):
+        """-> (flagged entries sorted by index - the candidate's number within the call -, their exact count, the lowest flagged
+        index or 2^64 - 1); out: a VERDICT_DTYPE array of the call's n entries to receive every verdict, or None"""
+        import numpy as np
+        fl = np.zeros(cap, dtype=T.VIOLATION_DTYPE)
+        cnt, first = C.c_uint64(0), C.c_uint64(0)
+        self._check(lib().demi_replay_batch_wait(self._h, ticket, out.ctypes.data if out is not None else None, fl.ctypes.data, cap,
+                                                 C.byref(cnt), C.byref(first)))
+        return fl[:min(cnt.value, cap)].copy(), int(cnt.value), int(first.value)
 
     def replay_batch_dev(self, d_masks_ptr, n, limits, d_out_ptr, stream=None):
         """Device-resident form: masks [n][4] u64 and verdicts [n] stay in HBM; enqueued on `stream`, not synchronised."""

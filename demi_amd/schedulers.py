@@ -336,6 +336,7 @@ class STSScheduler:
         self.schedulerConfig = schedulerConfig
         self.original_trace = original_trace
         self.p_max = p_max
+        self.chunk = 1 << 20                     # candidates per device call of a batch larger than this (two calls submitted ahead of the one waited for)
         self._ctx = _native.Context(device)
         self._ctx.model_load(schedulerConfig.model.to_struct())
         if getattr(schedulerConfig.model, "compiled_only", False):
@@ -364,19 +365,43 @@ class STSScheduler:
         reported as "does not reproduce"."""
         masks = self._masks(subseqs)
         lim = self._limits(violationFingerprint)
-        v = self._ctx.replay_batch(masks, lim)
+        v = self._replay(masks, lim)
         bad = np.nonzero(v["flags"] & OVF_FLAGS)[0]
         if len(bad):
             if lim.p_max < T.MAX_PENDING:
                 lim.p_max = T.MAX_PENDING
-                v[bad] = self._ctx.replay_batch(masks[bad], lim)
+                v[bad] = self._replay(masks[bad], lim)
             if (v["flags"] & OVF_FLAGS).any():
                 raise CapacityExceeded("%d candidate replay(s) exceed the engine's capacities" % int(((v["flags"] & OVF_FLAGS) != 0).sum()))
         return v
 
+    def _replay(self, masks, lim) -> np.ndarray:
+        """Every verdict of `masks`.  At most `chunk` candidates: one synchronous call (a DDMin frontier of 10 .. 4 096 candidates
+        is latency-bound: nothing to overlap).  More: calls of `chunk`, and while the answer of call k is waited for, calls k + 1
+        and k + 2 are already submitted in the one context (demi_replay_batch_submit / _wait: the tail of every launch is filled
+        by the next one, as in RandomScheduler.explore - GpuSTSScheduler.testBatch in scala/ is this loop)."""
+        n = len(masks)
+        if n <= self.chunk:
+            return self._ctx.replay_batch(masks, lim)
+        out = np.zeros(n, dtype=T.VERDICT_DTYPE)
+        ahead = []                                # the calls already submitted, in order: (first candidate, candidates, ticket)
+        nxt = 0
+        try:
+            while nxt < n or ahead:
+                while len(ahead) < 3 and nxt < n:
+                    m = min(self.chunk, n - nxt)
+                    ahead.append((nxt, m, self._ctx.replay_batch_submit(masks[nxt:nxt + m], lim, want_verdicts=True)))
+                    nxt += m
+                b, m, t = ahead.pop(0)
+                self._ctx.replay_batch_wait(t, out=out[b:b + m], cap=1)
+        finally:
+            while ahead:
+                self._ctx.replay_batch_wait(ahead.pop(0)[2], cap=1)
+        return out
+
     def test_batch(self, subseqs, violationFingerprint: ViolationFingerprint,
                    stats: Optional[MinimizationStats] = None) -> List[bool]:
-        """One K2 launch for a whole frontier; element i is True iff subseqs[i] reproduces the
+        """One K2 launch for a whole frontier (a batch of more than `chunk` candidates: calls of `chunk`, two in flight); element i is True iff subseqs[i] reproduces the
         violation (test() would return Some(trace)).  With a process group the candidates are dealt
         round-robin to the ranks and the verdict bits all-gathered."""
         from .distributed import sharded_map

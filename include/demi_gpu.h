@@ -1069,6 +1069,37 @@ int demi_random_explore_submit(demi_ctx* ctx, uint64_t seed_base, uint64_t n, co
 int demi_random_explore_wait(demi_ctx* ctx, uint32_t ticket, demi_verdict* out, demi_violation* flagged, uint32_t cap,
                              uint64_t* n_flagged, uint64_t* first_index);
 
+/* The replay oracle in pieces, two of them in flight (STSScheduler.test over a list of candidate subsequences, here cut into calls
+ * of n candidates each): the K1 pair above with candidates in place of executions.  demi_replay_batch_submit takes masks [n][4]
+ * as demi_replay_batch does, copies them to pinned memory of the ticket and enqueues their upload, the replay of the n candidates
+ * against the execution loaded by demi_replay_load and the compaction of the verdicts whose flags intersect flag_mask (0 =
+ * DEMI_V_VIOLATION) on a stream of the ctx's own; it returns at once with a ticket, and the caller's `masks` are its own again.
+ * demi_replay_batch_wait blocks until that call has finished and returns the flagged list - demi_violation.index is the
+ * candidate's number within the call; sorted by index, truncated to cap <= 65536; *n_flagged and *first_index (~0 when nothing
+ * is flagged) computed on the device, exact also when the list is truncated - and, if `out` is not NULL, all n verdicts: they are
+ * demi_replay_batch's bit for bit, for every table and filter_known_absents a plain replay takes (want_verdicts != 0 at the
+ * submit sends them to pinned memory of the library behind the call, so that the wait only copies them on with the CPU;
+ * otherwise the wait fetches them, on a stream that does not queue behind a launch submitted later).  With flag_mask =
+ * DEMI_V_VIOLATION | DEMI_V_PENDING_OVF | DEMI_V_QUEUE_OVF a DDMin driver reads from one answer the first reproducing candidate
+ * and whether a replay ABORTED on a capacity precedes it.
+ * Tickets: at most THREE replay tickets are outstanding, in slots of their own (three K1 tickets may be outstanding beside
+ * them); replay call k runs on stream k mod 2 and on the k mod 2-th set of K2's per-launch scratch; the loop to write is
+ * `submit(k + 2); wait(k)`, for the reasons given above.  Ids come from the one counter of the context, so a ticket names its
+ * kind: a replay ticket given to demi_random_explore_wait, or the reverse, is DEMI_ERR_INVALID_ARG with a message that says which
+ * kind it is; ticket 0, an unknown ticket and a second wait are refused with the same status.  A submit that fails leaves no slot
+ * busy.
+ * Ordering: every call that (re)loads what a replay reads - demi_replay_load, demi_model_load, demi_model_specialize, a replay
+ * with another filter_known_absents than the last one - waits for the launches in flight first: a ticket submitted before it
+ * stays waitable and answers for the execution and table loaded at its submit.  Synchronous calls of the same context between
+ * two submits (demi_replay_batch, the removal / wildcard batches, K1 tickets) are ordered with the tickets' launches by the
+ * events of the two scratch sets: they may cost overlap, never an answer.
+ * The remark on hardware queues above applies unchanged (the two streams are the same two). */
+int demi_replay_batch_submit(demi_ctx* ctx, const uint64_t* masks /* [n][4] */, uint64_t n, const demi_limits* limits,
+                             uint32_t flag_mask, uint32_t want_verdicts, uint32_t* ticket);
+int demi_replay_batch_wait(demi_ctx* ctx, uint32_t ticket, demi_verdict* out /* [n] or NULL */,
+                           demi_violation* flagged /* [cap] or NULL */, uint32_t cap,
+                           uint64_t* n_flagged, uint64_t* first_index);
+
 int demi_collect_violations_dev(demi_ctx* ctx, const demi_verdict* d_verdicts, uint64_t n, uint64_t index_base,
                                 demi_violation* d_out, uint32_t cap, unsigned long long* d_count,
                                 void* hip_stream);

@@ -249,6 +249,41 @@ JNIEXPORT jint JNICALL FN(replayBatch)(JNIEnv* e, jclass c, jlong h, jlongArray 
   PUT_LONGS(masks, m, JNI_ABORT);
   return rc;
 }
+/* replayBatch in pieces, two calls in flight in one context (single rank).  masks: long[4 * n], the library's own copy is taken before
+ * this returns.  Returns the ticket (> 0) or a negative demi_status. */
+JNIEXPORT jint JNICALL FN(replayBatchSubmit)(JNIEnv* e, jclass c, jlong h, jlongArray masks, jintArray limits, jint flagMask,
+                                            jboolean wantVerdicts) {
+  demi_limits lim;
+  uint32_t ticket = 0;
+  (void)c;
+  if (limits_of(e, limits, &lim) || LEN(masks) <= 0 || LEN(masks) % 4) return DEMI_ERR_INVALID_ARG;
+  void* m = LONGS(masks);
+  const int rc = LOST(masks, m) ? DEMI_ERR_INVALID_ARG
+                 : demi_replay_batch_submit(CTX(h), (const uint64_t*)m, (uint64_t)(LEN(masks) / 4), &lim, (uint32_t)flagMask,
+                                            wantVerdicts ? 1u : 0u, &ticket);
+  PUT_LONGS(masks, m, JNI_ABORT);
+  return rc ? rc : (jint)ticket;
+}
+/* n: the candidates of that submit (the library writes n verdicts: the array is checked against the caller's n, which must be the
+ * submit's); verdictsOrNull: long[2 * n]; out: long[2 * cap] (flagged entries, sorted by index); counts: long[2] = { number
+ * flagged, lowest flagged index } */
+JNIEXPORT jint JNICALL FN(replayBatchWait)(JNIEnv* e, jclass c, jlong h, jint ticket, jlong n, jlongArray verdictsOrNull, jlongArray out,
+                                          jlongArray counts) {
+  (void)c;
+  if (ticket <= 0 || n <= 0 || LEN(out) < 0 || LEN(out) % 2 || LEN(counts) != 2) return DEMI_ERR_INVALID_ARG;
+  if (verdictsOrNull && LEN(verdictsOrNull) < 2 * (int64_t)n) return DEMI_ERR_INVALID_ARG;
+  const uint32_t cap = (uint32_t)(LEN(out) / 2);
+  uint64_t n_flagged = 0, first = 0;
+  void* v = LONGS(verdictsOrNull);
+  void* o = LONGS(out);
+  jint rc = (LOST(verdictsOrNull, v) || LOST(out, o)) ? DEMI_ERR_INVALID_ARG
+            : demi_replay_batch_wait(CTX(h), (uint32_t)ticket, (demi_verdict*)v, (demi_violation*)o, cap, &n_flagged, &first);
+  PUT_LONGS(out, o, 0);
+  PUT_LONGS(verdictsOrNull, v, 0);
+  const jlong cn[2] = {(jlong)n_flagged, (jlong)first};
+  SET_LONGS(counts, 2, cn);
+  return rc;
+}
 JNIEXPORT jint JNICALL FN(replayRemovalBatch)(JNIEnv* e, jclass c, jlong h, jlongArray masksOrNull, jintArray skip, jintArray limits,
                                              jlongArray verdicts) {
   demi_limits lim;

@@ -35,6 +35,11 @@ object DemiGpu {
   @native def randomGetTraceCarried(h: Long, seed: Long, execIndex: Int, limits: Array[Int], verdict: Array[Long], recorded: Array[Byte]): Int
   @native def replayLoad(h: Long, externals: Array[Byte], recorded: Array[Byte]): Int
   @native def replayBatch(h: Long, masks: Array[Long], limits: Array[Int], verdicts: Array[Long]): Int
+  /** replayBatch in pieces, up to three calls outstanding in one context (demi_replay_batch_submit / _wait; the loop: submit(k + 2), wait(k)): the ticket (> 0) or a
+   *  negative status; `masks` may be reused as soon as submit returns.  wait: `n` is the submit's number of candidates, `verdictsOrNull` (long[2 * n]) receives every
+   *  verdict, `out` / `counts` the flagged candidates as randomExploreFlagged fills them (index = the candidate's number within the call) */
+  @native def replayBatchSubmit(h: Long, masks: Array[Long], limits: Array[Int], flagMask: Int, wantVerdicts: Boolean): Int
+  @native def replayBatchWait(h: Long, ticket: Int, n: Long, verdictsOrNull: Array[Long], out: Array[Long], counts: Array[Long]): Int
   @native def replayRemovalBatch(h: Long, masksOrNull: Array[Long], skip: Array[Int], limits: Array[Int], verdicts: Array[Long]): Int
   /** RunnerUtils.stsSchedDDMin in one call (demi_ddmin): params = int[4] (depth, max_candidates, check_unmodified, verify_mcs), mcs = long[4],
    *  stats = long[5] (consultations, launches, mcs_len, verified, replays) */

@@ -200,6 +200,11 @@ class GpuRandomScheduler(val schedulerConfig: SchedulerConfig, max_executions: I
   def shutdown() { ctxDestroy(h) }
 }
 
+object GpuSTSScheduler {
+  /** candidates per device call of a testBatch larger than this (2^20, as GpuRandomScheduler.CHUNK) */
+  val CHUNK = 1 << 20
+}
+
 /** STSScheduler(schedulerConfig, original_trace, allowPeek = false) as DDMin's oracle (STSScheduler.scala:199-310). */
 class GpuSTSScheduler(val schedulerConfig: SchedulerConfig, original_trace: EventTrace, lowering: TableLowering,
                       device: Int = 0, pMax: Int = 64) extends GpuSchedulerBase with TestOracle {
@@ -234,13 +239,40 @@ class GpuSTSScheduler(val schedulerConfig: SchedulerConfig, original_trace: Even
     m
   }
 
-  /** one launch for a whole DDMin frontier: element i is Some(executed trace) iff subseqs(i) reproduces the violation */
+  /** A batch of more than CHUNK candidates: calls of CHUNK, and while the answer of call k is waited for, calls k + 1 and k + 2 are
+   *  already submitted in the one context (demi_replay_batch_submit / _wait: the tail of every launch is filled by the next one,
+   *  as in GpuRandomScheduler.explore).  Fills `v` with what one replayBatch of all of them returns. */
+  private def replayPipelined(masks: Array[Long], n: Int, lim: Array[Int], v: Array[Long]) {
+    val chunk = GpuSTSScheduler.CHUNK
+    val ahead = scala.collection.mutable.Queue[(Int, Int, Int)]()    // (first candidate, candidates, ticket), in order
+    val none = new Array[Long](0); val counts = new Array[Long](2)
+    var nxt = 0
+    try {
+      while (nxt < n || ahead.nonEmpty) {
+        while (ahead.size < 3 && nxt < n) {
+          val m = math.min(chunk, n - nxt)
+          ahead.enqueue((nxt, m, check(h, replayBatchSubmit(h, java.util.Arrays.copyOfRange(masks, 4 * nxt, 4 * (nxt + m)), lim, V_VIOLATION, true))))
+          nxt += m
+        }
+        val (b, m, t) = ahead.dequeue()
+        val part = new Array[Long](2 * m)
+        check(h, replayBatchWait(h, t, m, part, none, counts))
+        System.arraycopy(part, 0, v, 2 * b, 2 * m)
+      }
+    } finally {
+      while (ahead.nonEmpty) { val (_, m, t) = ahead.dequeue(); replayBatchWait(h, t, m, null, none, counts) }
+    }
+  }
+
+  /** one launch for a whole DDMin frontier (a batch of more than CHUNK candidates: calls of CHUNK, two in flight): element i is
+   *  Some(executed trace) iff subseqs(i) reproduces the violation */
   def testBatch(subseqs: Seq[Seq[ExternalEvent]], fp: ViolationFingerprint, stats: MinimizationStats): Seq[Option[EventTrace]] = {
     requireInvariant()
     if (stats != null) subseqs.foreach(_ => stats.increment_replays())
     val masks = subseqs.flatMap(mask).toArray
     val v = new Array[Long](2 * subseqs.size)
-    check(h, replayBatch(h, masks, limits(fp), v))
+    if (subseqs.size <= GpuSTSScheduler.CHUNK) check(h, replayBatch(h, masks, limits(fp), v))
+    else replayPipelined(masks, subseqs.size, limits(fp), v)
     val OVF = V_PENDING_OVF | V_QUEUE_OVF
     subseqs.indices.map { i =>
       var f = flags(v, i)
