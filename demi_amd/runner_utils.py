@@ -104,7 +104,8 @@ def fuzz_campaign(fuzzer_args, schedulerConfig: SchedulerConfig,
     before the reported one was aborted on a capacity, the campaign goes on with the largest pending set (fuzz() decides such an
     execution alone with it; verdicts without an overflow do not depend on p_max); CapacityExceeded if that does not suffice."""
     from . import _native
-    from .schedulers import CapacityExceeded, SrcDstFIFO
+    from .capacity import CapacityExceeded, is_largest, largest
+    from .schedulers import SrcDstFIFO
     num_events, weights, send_gen, prefix = fuzzer_args[:4]
     postfix = fuzzer_args[4] if len(fuzzer_args) > 4 else ()
     model = schedulerConfig.model
@@ -136,9 +137,9 @@ def fuzz_campaign(fuzzer_args, schedulerConfig: SchedulerConfig,
                 # an execution aborted on a capacity has no verdict.  fuzz() decides it alone with the largest pending set; a verdict
                 # does not depend on p_max unless the execution overflows, so the campaign from this test on with the largest
                 # pending set answers what fuzz() answers.  Aborts that remain are beyond the engine, as they are for fuzz().
-                if lim.p_max >= T.MAX_PENDING:
+                if is_largest(lim.p_max):
                     raise CapacityExceeded("%d tests of the campaign have executions beyond p_max = %d" % (res.capacity_aborts, lim.p_max))
-                lim.p_max = T.MAX_PENDING
+                lim = largest(lim)
                 continue
             if not res.found:
                 return None

@@ -19,6 +19,7 @@ import numpy as np
 
 from . import _native
 from . import types as T
+from .capacity import CapacityExceeded, OVF_FLAGS, aborted, decide_batch, decide_one, is_largest, largest  # noqa: F401 (re-exported)
 from .model import Model
 
 
@@ -233,25 +234,8 @@ class RandomScheduler:
                 hits, n_hits, first = self._ctx.random_explore_wait(cur[2])
                 # a truncated list is an arbitrary subset: only the lowest index (computed on the device) is certain then
                 cand = [(int(h["index"]), int(h["flags"])) for h in hits] if n_hits <= len(hits) else [(first, None)]
-                nxt = start + span
-                for idx, flags in cand:
-                    if flags is not None and not (flags & OVF_FLAGS):
-                        i = start + idx
-                        break
-                    # aborted (or unknown): decide this execution alone
-                    self.last_aborted_reruns += 1
-                    big = self._limits(_lookingFor)
-                    big.p_max = T.MAX_PENDING
-                    v1, _ = self._ctx.random_get_trace(self.seed_base + start + idx, big)
-                    if v1.flags & OVF_FLAGS:
-                        raise CapacityExceeded("schedule %d exceeds the engine's capacities (flags 0x%x)" % (start + idx, v1.flags & 0xFF))
-                    if v1.flags & T.V_VIOLATION:
-                        i = start + idx
-                        lim = big
-                        break
-                    if flags is None:
-                        nxt = start + idx + 1
-                start = nxt
+                i, lim, nxt = self._settle(start, cand, lim)
+                start = start + span if nxt is None else nxt
         finally:
             drain()
         if i is None:
@@ -262,6 +246,27 @@ class RandomScheduler:
         used = ev[:T.verdict_trace_idx(v.flags)]
         mask = self._model.fp_match_mask if self._model else 0xFFFFFFFF
         return EventTrace(rec, used, kept_areas(len(used))), ViolationFingerprint(int(v.fingerprint), mask)
+
+    def _settle(self, start, cand, lim):
+        """The flagged executions cand = [(index, flags; None = unknown)] of the call that began at execution `start`, lowest first:
+        an aborted or unknown one is decided alone with the largest pending set before any higher index is believed.  -> (the first
+        violating execution or None, the limits it violates under, where the search goes on behind a clean unknown one or None)."""
+        nxt = None
+        for idx, flags in cand:
+            if flags is not None and not (flags & OVF_FLAGS):
+                return start + idx, lim, nxt
+            if flags is not None and is_largest(lim.p_max):
+                raise CapacityExceeded("schedule %d exceeds the engine's capacities (flags 0x%x)" % (start + idx, flags & 0xFF))
+            self.last_aborted_reruns += 1
+            big = largest(lim)
+            v1, _ = self._ctx.random_get_trace(self.seed_base + start + idx, big)
+            if v1.flags & OVF_FLAGS:
+                raise CapacityExceeded("schedule %d exceeds the engine's capacities (flags 0x%x)" % (start + idx, v1.flags & 0xFF))
+            if v1.flags & T.V_VIOLATION:
+                return start + idx, big, nxt
+            if flags is None:
+                nxt = start + idx + 1
+        return None, lim, nxt
 
     def _explore_one_call(self, ev, _lookingFor):
         """explore() as rounds 1-5 ran it: ONE device call for all the executions (kept for the comparison in the suite)."""
@@ -275,28 +280,10 @@ class RandomScheduler:
                 return None
             # a truncated list is an arbitrary subset: only the lowest index (computed on the device) is certain then
             cand = [(int(h["index"]), int(h["flags"])) for h in hits] if n_hits <= len(hits) else [(first, None)]
-            nxt = self.max_executions
-            for idx, flags in cand:
-                if flags is not None and not (flags & OVF_FLAGS):
-                    i = start + idx
-                    break
-                # aborted (or unknown): decide this execution alone
-                self.last_aborted_reruns += 1
-                big = self._limits(_lookingFor)
-                big.p_max = T.MAX_PENDING
-                v1, _ = self._ctx.random_get_trace(self.seed_base + start + idx, big)
-                if v1.flags & OVF_FLAGS:
-                    raise CapacityExceeded("schedule %d exceeds the engine's capacities (flags 0x%x)" % (start + idx, v1.flags & 0xFF))
-                if v1.flags & T.V_VIOLATION:
-                    i = start + idx
-                    lim = big
-                    break
-                if flags is None:
-                    nxt = start + idx + 1
-            else:
-                if n_hits <= len(hits):
-                    return None           # every flagged execution was an abort that turned out clean
-            start = nxt
+            i, lim, nxt = self._settle(start, cand, lim)
+            if i is None and n_hits <= len(hits):
+                return None               # every flagged execution was an abort that turned out clean
+            start = nxt if i is None else start
         if i is None:
             return None
         v, rec = self._ctx.random_get_trace(self.seed_base + i, lim)
@@ -364,16 +351,8 @@ class STSScheduler:
         pending set, and if it still does not fit the candidate cannot be decided here (CapacityExceeded) - never
         reported as "does not reproduce"."""
         masks = self._masks(subseqs)
-        lim = self._limits(violationFingerprint)
-        v = self._replay(masks, lim)
-        bad = np.nonzero(v["flags"] & OVF_FLAGS)[0]
-        if len(bad):
-            if lim.p_max < T.MAX_PENDING:
-                lim.p_max = T.MAX_PENDING
-                v[bad] = self._replay(masks[bad], lim)
-            if (v["flags"] & OVF_FLAGS).any():
-                raise CapacityExceeded("%d candidate replay(s) exceed the engine's capacities" % int(((v["flags"] & OVF_FLAGS) != 0).sum()))
-        return v
+        return decide_batch(lambda l, idx: self._replay(masks if idx is None else masks[idx], l), self._limits(violationFingerprint), aborted,
+                            lambda n: "%d candidate replay(s) exceed the engine's capacities" % n)[0]
 
     def _replay(self, masks, lim) -> np.ndarray:
         """Every verdict of `masks`.  At most `chunk` candidates: one synchronous call (a DDMin frontier of 10 .. 4 096 candidates
@@ -424,28 +403,15 @@ class STSScheduler:
         the input of internal-event minimization."""
         from .internal_minimization import executed_trace
         subseq = tuple(subseq)
-        lim = self._limits(violationFingerprint)
-        v, kept = self._ctx.replay_get_kept(len(self.original_trace.events), 0xFFFFFFFF, lim, mask=self._masks([subseq])[0])
-        if (int(v.flags) & OVF_FLAGS) and lim.p_max < T.MAX_PENDING:
-            lim.p_max = T.MAX_PENDING
-            v, kept = self._ctx.replay_get_kept(len(self.original_trace.events), 0xFFFFFFFF, lim, mask=self._masks([subseq])[0])
-        if int(v.flags) & OVF_FLAGS:
-            raise CapacityExceeded("the replay exceeds the engine's capacities")
+        mask = self._masks([subseq])[0]
+        v, kept = decide_one(lambda l: self._ctx.replay_get_kept(len(self.original_trace.events), 0xFFFFFFFF, l, mask=mask),
+                             self._limits(violationFingerprint))
         if not (int(v.flags) & T.V_VIOLATION):
             return None
         return executed_trace(self.original_trace, kept, subseq=subseq)
 
     def shutdown(self):
         self._ctx.close()
-
-
-class CapacityExceeded(RuntimeError):
-    """An execution needed more than the engine's largest capacities (pending set of DEMI_MAX_PENDING messages, the
-    timer queues, DEMI_FX_CAP effects per delivery): its verdict is invalid (DEMI_V_PENDING_OVF / DEMI_V_QUEUE_OVF) and the
-    reference, which has no such capacities, must decide it (JVM fallback)."""
-
-
-OVF_FLAGS = T.V_PENDING_OVF | T.V_QUEUE_OVF
 
 
 class ReplayException(Exception):

@@ -21,6 +21,7 @@ import numpy as np
 
 from . import _native
 from . import types as T
+from .capacity import aborted, decide_batch, decide_one
 from .internal_minimization import countMsgEvents
 from .model import Model
 from .schedulers import EventTrace, MinimizationStats, SchedulerConfig, ViolationFingerprint
@@ -336,53 +337,41 @@ class StsWildcardOracle:
         self._ctx.replay_wildcard_load(type_sets, policies)
         self._trace = trace
 
+    def _counted(self, launch):               # `launch` with every call of it counted
+        def run(*args):
+            self.launches += 1
+            return launch(*args)
+        return run
+
     def test_batch(self, presents: Sequence[np.ndarray], violation: ViolationFingerprint, masks=None) -> List[bool]:
         """masks (uint64[n, 4], optional): the subsequence of the LOADED externals every candidate keeps - the trace stays
         loaded with its own externals, so that the records' ext_idx stay aligned."""
-        from .schedulers import CapacityExceeded, OVF_FLAGS
         presents = np.asarray(presents, dtype=bool).reshape(len(presents), -1)
         if masks is not None:
             masks = np.ascontiguousarray(masks, dtype=np.uint64).reshape(-1, 4)
-        self.launches += 1
         self.batches.append(len(presents))
-        v = self._ctx.replay_wildcard_batch(presents, self._limits(violation), masks=masks)
-        bad = np.nonzero(v["flags"] & OVF_FLAGS)[0]
-        if len(bad):      # a replay aborted on a capacity is no answer: repeat it with the largest pending set, else give up loudly
-            self.launches += 1
-            v[bad] = self._ctx.replay_wildcard_batch(presents[bad], self._limits(violation, T.MAX_PENDING),
-                                                     masks=None if masks is None else masks[bad])
-            if (v["flags"] & OVF_FLAGS).any():
-                raise CapacityExceeded("a wildcard candidate's replay exceeds the engine's capacities")
+        sub = lambda a, idx: a if a is None or idx is None else a[idx]
+        v, _ = decide_batch(self._counted(lambda l, idx: self._ctx.replay_wildcard_batch(sub(presents, idx), l, masks=sub(masks, idx))),
+                            self._limits(violation), aborted, "a wildcard candidate's replay exceeds the engine's capacities")
         return [bool(f & T.V_VIOLATION) for f in v["flags"]]
 
     def test_candidates(self, masks, drops, violation: ViolationFingerprint, base_present=None) -> np.ndarray:
         """One WildcardTestOracle.test per row of masks (demi_replay_wildcard_candidates): WILDCARD_CANDIDATE_DTYPE records.
         A candidate that is unknown because of a capacity is evaluated again with the largest pending set."""
-        from .schedulers import CapacityExceeded
         masks = np.ascontiguousarray(masks, dtype=np.uint64).reshape(-1, 4)
-        self.launches += 1
         self.batches.append(len(masks))
-        r = self._ctx.replay_wildcard_candidates(masks, drops, self._limits(violation), base_present=base_present)
-        bad = np.nonzero(r["flags"] & T.WC_UNKNOWN)[0]
-        if len(bad):
-            self.launches += 1
-            self.retried = getattr(self, "retried", 0) + len(bad)
-            r[bad] = self._ctx.replay_wildcard_candidates(masks[bad], drops, self._limits(violation, T.MAX_PENDING), base_present=base_present)
-            if (r["flags"] & T.WC_UNKNOWN).any():
-                raise CapacityExceeded("a wildcard candidate's proposal exceeds the engine's capacities")
+        r, again = decide_batch(self._counted(lambda l, idx: self._ctx.replay_wildcard_candidates(masks if idx is None else masks[idx], drops, l,
+                                                                                                  base_present=base_present)),
+                                self._limits(violation), lambda r: (r["flags"] & T.WC_UNKNOWN) != 0,
+                                "a wildcard candidate's proposal exceeds the engine's capacities")
+        if again:
+            self.retried = getattr(self, "retried", 0) + again
         return r
 
     def executed(self, present: np.ndarray, violation: ViolationFingerprint, mask=None):
         """test() of one candidate: (executed trace, record indices of the present deliveries that were ignored as absent)
         iff it triggers the violation, else None.  mask: as in test_batch."""
-        from .schedulers import CapacityExceeded, OVF_FLAGS
-        self.launches += 1
-        v, kept, rec = self._ctx.replay_wildcard_get_trace(present, self._limits(violation), mask=mask)
-        if (int(v.flags) & OVF_FLAGS) and self.p_max < T.MAX_PENDING:
-            self.launches += 1
-            v, kept, rec = self._ctx.replay_wildcard_get_trace(present, self._limits(violation, T.MAX_PENDING), mask=mask)
-        if int(v.flags) & OVF_FLAGS:
-            raise CapacityExceeded("the replay exceeds the engine's capacities")
+        v, kept, rec = decide_one(self._counted(lambda l: self._ctx.replay_wildcard_get_trace(present, l, mask=mask)), self._limits(violation))
         if not (int(v.flags) & T.V_VIOLATION):
             return None
         ev = self._trace.events

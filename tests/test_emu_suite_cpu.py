@@ -129,6 +129,15 @@ def test_k2_sources_against_the_oracle_on_the_cpu():
                   "test_k2_gpu.py::test_native_ddmin_equals_the_python_mirror_on_the_gpu"])
 
 
+def test_capacity_rule_at_every_site_on_the_cpu():
+    """A replay aborted on a capacity is run once more with the largest pending set: demi_ddmin, demi_random_ddmin and the Python
+    oracles under a pending set so small that a replay they consult aborts (tests/test_capacity_retry_gpu.py, its cheapest cases)."""
+    run_emulated(["test_capacity_retry_gpu.py::test_ddmin_under_a_small_pending_set",
+                  "test_capacity_retry_gpu.py::test_sts_scheduler_under_a_small_pending_set",
+                  "test_capacity_retry_gpu.py::test_removal_oracle_under_a_small_pending_set",
+                  "test_capacity_retry_gpu.py::test_random_ddmin_under_a_small_pending_set"])
+
+
 def test_k3_and_provenance_sources_against_the_oracle_on_the_cpu():
     # (one OS thread: the explored-pair table's bounded wait for a half-published key assumes the publishing wave is running)
     run_emulated(["test_k3_gpu.py::test_per_interleaving_outputs_match_the_oracle",
