@@ -241,6 +241,26 @@ inline std::string tq_defines(const demi::DevModel& h) {
   return buf;
 }
 
+// ------------------------------------------------------------------ K1's hit mask of a fresh execution
+// The invariant's per-actor hit of the INITIAL states (sim_core.hpp invariant_hit_at: bit a = F[inv_fa] of actor a's initial state
+// equals inv_va, or is non-zero for AGREE) is a function of the table alone, so a kernel compiled for it gets it as a constant
+// next to DEMI_JIT_INV_KIND.  A DEMI_INV_PROGRAM invariant gets no line: the kernel runs the program once per lane before its loop.
+inline std::string init_hits_define(const demi::DevModel& h) {
+  if ((h.inv_kind & DEMI_INV_PROGRAM) || h.inv_fa >= 8u) return "";
+  const bool big = h.n_actors > DEMI_MAX_ACTORS;
+  uint32_t hits = 0;
+  for (uint32_t a = 0; a < h.n_actors; a++) {
+    const uint32_t f = h.inv_fa;
+    uint32_t v;
+    if (big || h.wide) v = (uint32_t)((big ? h.init_state_big : h.init_state_wide)[2 * a + (f >> 2)] >> (16 * (f & 3))) & 0xFFFFu;
+    else v = (uint32_t)(h.init_state[a] >> (8 * f)) & 0xFFu;
+    hits |= (uint32_t)(((h.inv_kind & 0xFFu) == DEMI_INV_AGREE) ? (v != 0) : (v == h.inv_va)) << a;
+  }
+  char buf[64];
+  snprintf(buf, sizeof buf, "#define DEMI_JIT_INIT_HITS 0x%xu\n", hits);
+  return buf;
+}
+
 // ------------------------------------------------------------------ code generation
 // One statement block per row; forward skips become gotos (the table has no backward edges, validation
 // guarantees it), handler entry is a switch over the distinct handler starts.

@@ -175,6 +175,11 @@ __host__ __device__ inline size_t k1_lds_bytes(uint32_t code_len, uint32_t n_ev,
                      k1_tdir_wave_bytes(n_actors, n_timer_types)) + k1_rb_bytes(rb_words, rb_classes);
 }
 
+// A kernel compiled for one table (it knows the actor count) copies the initial states and hashes the final ones through
+// registers, several LDS loads per wait; the interpreter keeps the word-by-word loops.  (DEMI_K1_NO_ST_BATCH: those, for A/B runs)
+#if defined(DEMI_JIT_A) && !defined(DEMI_K1_NO_ST_BATCH)
+#define DEMI_K1_ST_BATCH 1
+#endif
 #ifdef DEMI_K1_MIN_WAVES_PER_EU    // experiment knob of the specialised build: ask for more waves per SIMD (fewer VGPRs)
 #define K1_LAUNCH_BOUNDS __launch_bounds__(K1_WAVES * 64, DEMI_K1_MIN_WAVES_PER_EU)
 #else
@@ -636,15 +641,22 @@ __global__ K1_LAUNCH_BOUNDS void k1_random_explore(const typename K1ArgsOf<V>::t
   // rw = the word that leaves slot idx.  The timer directory follows: a removed timer whose entry points at idx has no
   // copy left (an entry only points somewhere while that copy is the single one), a timer moved out of the last slot
   // takes its entry along.
-  auto pend_remove = [&](uint32_t idx, word_t rw, word_t lw) {
+  // pend_remove_moved is the part that does not look at rw: for a caller that has settled the removed word's entry itself (a
+  // cancel holds the entry it found the slot through: it writes TD_NONE there, or the entry is TD_MANY and stays so until the
+  // cancel repairs it - nothing to decode, re-read or compare).  DEMI_K1_NO_RM_KNOWN: cancels use the general form, for A/B runs.
+  auto pend_remove_moved = [&](uint32_t idx, word_t lw) {
     const uint32_t last = n_pend - 1;
     pend_store(mem, idx, lw);
     if (REC) aux_store(mem, idx, aux_load(mem, last));
     uint32_t e;
-    if (timer_entry(rw, e)) { unsigned char* const p = td_ptr(e); if (*p == idx) *p = (unsigned char)TD_NONE; }
     if (idx != last && timer_entry(lw, e)) { unsigned char* const p = td_ptr(e); if (*p == last) *p = (unsigned char)idx; }
     n_pend = last;
     LASTW_RELOAD();          // (after the store above: when idx is the new last slot the load returns lw, same lane, same address)
+  };
+  auto pend_remove = [&](uint32_t idx, word_t rw, word_t lw) {
+    uint32_t e;
+    if (timer_entry(rw, e)) { unsigned char* const p = td_ptr(e); if (*p == idx) *p = (unsigned char)TD_NONE; }
+    pend_remove_moved(idx, lw);
   };
   // the directory from scratch (after the blocked-actor path has permuted the array)
   auto tdir_rebuild = [&]() {
@@ -674,6 +686,21 @@ __global__ K1_LAUNCH_BOUNDS void k1_random_explore(const typename K1ArgsOf<V>::t
     if (args.looking_for_valid && (!CARRY || exec_no == 0)) return (((fp ^ args.looking_for) & fp_mask) == 0) ? args.looking_for : 0u;
     return fp;
   };
+  // The hit mask a fresh execution starts with: a function of the initial states alone (the candidates of MULTI and TESTS differ
+  // in `exists`, which masks it at check time).  A compiled table brings it as a constant (jit.hpp init_hits_define); otherwise it
+  // is computed here, once, on this lane's own state words, and kept in a scalar register - it is the same for every lane.  A
+  // DEMI_INV_PEERS program rebuilds the mask at every check, whatever it starts from.  (DEMI_K1_NO_INIT_HITS: recompute per
+  // execution, for A/B runs.)
+#if defined(DEMI_JIT_INIT_HITS) && !defined(DEMI_K1_NO_INIT_HITS)
+  const uint32_t init_hits = DEMI_JIT_INIT_HITS;
+#elif !defined(DEMI_K1_NO_INIT_HITS)
+  uint32_t init_hits = 0;
+  if (!(inv_kind & DEMI_INV_PEERS)) {
+    for (uint32_t i = 0; i < A * ST_WORDS; i++) st[i * 64] = t.init[i];
+    for (uint32_t a = 0; a < A; a++) init_hits |= invariant_hit_at(t, st, a, inv_kind, inv_fa, inv_va) << a;
+    init_hits = (uint32_t)__builtin_amdgcn_readfirstlane((int)init_hits);
+  }
+#endif
 
 #ifdef DEMI_K1_PHASES
   uint64_t ph_t[14] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, ph_iters = 0, ph_active = 0;
@@ -711,7 +738,18 @@ __global__ K1_LAUNCH_BOUNDS void k1_random_explore(const typename K1ArgsOf<V>::t
       if (ph == PH_FINISH) {
         // explore(): `if (messagesScheduledSoFar <= maxMessages) checkIfBugFound` (:256-262, 156-180)
         if (!(flags & (DEMI_OVF_ANY | DEMI_V_MAXMSG)) && !viol) viol = check_invariant();
+#ifndef DEMI_K1_ST_BATCH
         for (uint32_t i = 0; i < A * ST_WORDS; i++) hash_step(hash, st[i * 64]);
+#else
+        // (the state words eight at a time into registers - one wait for the loads - then the FNV chain over them)
+        for (uint32_t i0 = 0; i0 < A * ST_WORDS; i0 += 8) {
+          uint64_t sv[8];
+#pragma unroll
+          for (uint32_t k = 0; k < 8; k++) if (i0 + k < A * ST_WORDS) sv[k] = st[(i0 + k) * 64];
+#pragma unroll
+          for (uint32_t k = 0; k < 8; k++) if (i0 + k < A * ST_WORDS) hash_step(hash, sv[k]);
+        }
+#endif
         uint4 v;
         if (flags & DEMI_OVF_ANY) {
           v.x = flags & DEMI_OVF_ANY; v.y = 0; v.z = 0; v.w = 0;
@@ -806,10 +844,25 @@ __global__ K1_LAUNCH_BOUNDS void k1_random_explore(const typename K1ArgsOf<V>::t
           hash = 0xCBF29CE484222325ULL;
           net.inaccessible = exists; net.killed = 0; pairs_clear(net.partitioned);
           blocked = 0;
-          hits = 0;
           for (uint32_t j = 0; j < k1_tdir_words(A, NTT); j++) *reinterpret_cast<uint32_t*>(tdir + (j << 8)) = 0xFFFFFFFFu;   // no timer pending
+#ifndef DEMI_K1_ST_BATCH
           for (uint32_t i = 0; i < A * ST_WORDS; i++) st[i * 64] = t.init[i];
+#else
+          // (the table's initial states and this lane's state words never overlap: eight loads in flight, one wait, eight stores)
+          for (uint32_t i0 = 0; i0 < A * ST_WORDS; i0 += 8) {
+            uint64_t iv[8];
+#pragma unroll
+            for (uint32_t k = 0; k < 8; k++) if (i0 + k < A * ST_WORDS) iv[k] = t.init[i0 + k];
+#pragma unroll
+            for (uint32_t k = 0; k < 8; k++) if (i0 + k < A * ST_WORDS) st[(i0 + k) * 64] = iv[k];
+          }
+#endif
+#ifdef DEMI_K1_NO_INIT_HITS
+          hits = 0;
           for (uint32_t a = 0; a < A; a++) hits |= invariant_hit_at(t, st, a, inv_kind, inv_fa, inv_va) << a;
+#else
+          hits = init_hits;
+#endif
           if (REC) { rec = args.rec_out + (args.rec_shared ? 0ull : sched * (uint64_t)args.rec_cap); n_rec = 0; next_id = 1; }
           batch_no = 0;
         }
@@ -1228,7 +1281,12 @@ __global__ K1_LAUNCH_BOUNDS void k1_random_explore(const typename K1ArgsOf<V>::t
         if (d != TD_NONE) {
           const word_t wantw = msg_word(type, DL, me, 0, 0);
           if (d != TD_MANY) {
+#ifdef DEMI_K1_NO_RM_KNOWN
             pend_remove(d, wantw, LASTW());
+#else
+            *p = (unsigned char)TD_NONE;            // (the single copy leaves; a word moved out of the last slot is another timer's)
+            pend_remove_moved(d, LASTW());
+#endif
           } else {
             // several copies were pending at some point: scan.  The scan also counts the copies, so the entry becomes exact
             // again when at most one is left after this removal.
@@ -1240,7 +1298,11 @@ __global__ K1_LAUNCH_BOUNDS void k1_random_explore(const typename K1ArgsOf<V>::t
               }
             if (copies != 0) {
               const uint32_t last = n_pend - 1;
+#ifdef DEMI_K1_NO_RM_KNOWN
               pend_remove(first, wantw, LASTW());   // (the entry is TD_MANY: pend_remove leaves it alone)
+#else
+              pend_remove_moved(first, LASTW());    // (the entry is TD_MANY: neither the removed nor a moved copy changes it)
+#endif
               if (copies == 2) *p = (unsigned char)(second == last ? first : second);
             }
             if (copies <= 1) *p = (unsigned char)TD_NONE;
