@@ -22,6 +22,7 @@ EXPORTS = ["demi_ctx_create", "demi_ctx_destroy", "demi_last_error", "demi_versi
            "demi_replay_wildcard_candidates", "demi_wildcard_ddmin",
            "demi_fuzz_stride", "demi_fuzz_generate", "demi_random_explore_tests", "demi_fuzz_campaign",
            "demi_fuzz_generate_fields", "demi_random_explore_tests_areas", "demi_fuzz_campaign_fields",
+           "demi_fuzz_launch_summary", "demi_fuzz_launch_summary_row", "demi_fuzz_campaign_pipelined",
            "demi_replay_removal_round", "demi_minimize_internals", "demi_replay_wildcard_round", "demi_minimize_wildcards",
            "demi_replay_batch_submit", "demi_replay_batch_wait"]
 
@@ -161,6 +162,11 @@ def lib():
                                                   C.POINTER(T.Limits), C.c_void_p, C.c_void_p]
     L.demi_fuzz_campaign_fields.argtypes = [C.c_void_p, C.POINTER(T.FuzzParams), C.POINTER(T.FuzzFieldGen), C.POINTER(T.FuzzCampaignParams),
                                             C.POINTER(T.Limits), C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(T.FuzzCampaignResult)]
+    L.demi_fuzz_launch_summary.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(T.FuzzSummary)]
+    L.demi_fuzz_launch_summary_row.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]
+    L.demi_fuzz_campaign_pipelined.argtypes = [C.c_void_p, C.POINTER(T.FuzzParams), C.POINTER(T.FuzzFieldGen), C.POINTER(T.FuzzCampaignParams),
+                                               C.POINTER(T.FuzzPipelineParams), C.POINTER(T.Limits), C.c_void_p, C.c_void_p, C.c_uint32,
+                                               C.POINTER(T.FuzzCampaignResult), C.POINTER(T.FuzzPipelineStats)]
     L.demi_replay_removal_round.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(T.Limits), C.c_void_p,
                                             C.POINTER(T.RemovalRoundResult)]
     L.demi_minimize_internals.argtypes = [C.c_void_p, C.POINTER(T.Limits), C.POINTER(T.IntminParams), C.c_void_p, C.c_uint32,
@@ -510,18 +516,59 @@ class Context:
                                                     v.ctypes.data, f.ctypes.data))
         return v, f
 
+    def fuzz_launch_summary(self, n_tests, executions, flags=None, verdicts=None, row=False):
+        """demi_fuzz_launch_summary: the T.FuzzSummary of a launch's flags [n_tests] and verdicts [n_tests, executions] (both, or
+        neither: the results the last random_explore_tests(None, ..) left on the device).  row=True: (summary, the hit test's events or
+        None, its payload areas or None) - demi_fuzz_launch_summary_row."""
+        import numpy as np
+        fp = vp = None
+        if flags is not None:
+            flags = np.ascontiguousarray(flags, dtype=np.uint32)
+            assert flags.shape == (n_tests,)
+            fp = flags.ctypes.data
+        if verdicts is not None:
+            verdicts = np.ascontiguousarray(verdicts, dtype=T.VERDICT_DTYPE)
+            assert verdicts.size == n_tests * executions
+            vp = verdicts.ctypes.data
+        s = T.FuzzSummary()
+        self._check(lib().demi_fuzz_launch_summary(self._h, fp, vp, n_tests, executions, C.byref(s)))
+        if not row:
+            return s
+        if s.first_hit >= n_tests:
+            return s, None, None
+        ev = np.zeros(T.MAX_EXT_EVENTS, dtype=T.EXT_EVENT_DTYPE)
+        ar = np.zeros(T.MAX_EXT_EVENTS, dtype=np.uint64)
+        self._check(lib().demi_fuzz_launch_summary_row(self._h, ev.ctypes.data, ar.ctypes.data, T.MAX_EXT_EVENTS))
+        return s, ev[:s.n_events].copy(), ar[:s.n_events].copy()
+
     def fuzz_campaign(self, num_events, weights, send_gen, prefix, limits, postfix=(), executions_per_test=1, tests_per_launch=256,
-                      max_tests=1024, test_seed_base=0, exec_seed_base=0):
+                      max_tests=1024, test_seed_base=0, exec_seed_base=0, in_flight=None, cap=None):
         """demi_fuzz_campaign: (result struct, the violating test's events or None).  With a fuzzer.FieldSendGenerator
-        (demi_fuzz_campaign_fields): (result struct, events or None, their payload areas or None)."""
+        (demi_fuzz_campaign_fields): (result struct, events or None, their payload areas or None).
+        in_flight=1..3 (0 = 2): demi_fuzz_campaign_pipelined, that many launches on the device at a time - the same answers; its
+        T.FuzzPipelineStats is left in self.fuzz_pipeline_stats.  None: the synchronous entry points.  cap: the events the output
+        holds (default: the largest test)."""
         import numpy as np
         from . import fuzzer as F
         par, keep = self.fuzz_params(num_events, weights, send_gen, prefix, postfix)
         cp = T.FuzzCampaignParams(test_seed_base=test_seed_base, exec_seed_base=exec_seed_base, executions_per_test=executions_per_test,
                                   tests_per_launch=tests_per_launch, max_tests=max_tests)
         res = T.FuzzCampaignResult()
-        cap = T.MAX_EXT_EVENTS
-        ev = np.zeros(cap, dtype=T.EXT_EVENT_DTYPE)
+        cap = T.MAX_EXT_EVENTS if cap is None else cap
+        ev = np.zeros(max(cap, 1), dtype=T.EXT_EVENT_DTYPE)
+        if in_flight is not None:
+            fields = isinstance(send_gen, F.FieldSendGenerator)
+            fg = self.field_gen_struct(send_gen) if fields else None
+            ar = np.zeros(max(cap, 1), dtype=np.uint64)
+            pp = T.FuzzPipelineParams(in_flight=in_flight)
+            self.fuzz_pipeline_stats = st = T.FuzzPipelineStats()
+            self._check(lib().demi_fuzz_campaign_pipelined(self._h, C.byref(par), C.byref(fg) if fields else None, C.byref(cp), C.byref(pp),
+                                                           C.byref(limits), ev.ctypes.data, ar.ctypes.data if fields else None, cap,
+                                                           C.byref(res), C.byref(st)))
+            del keep
+            if fields:
+                return (res, ev[:res.n_events].copy(), ar[:res.n_events].copy()) if res.found else (res, None, None)
+            return res, (ev[:res.n_events].copy() if res.found else None)
         if isinstance(send_gen, F.FieldSendGenerator):
             fg = self.field_gen_struct(send_gen)
             ar = np.zeros(cap, dtype=np.uint64)

@@ -87,7 +87,8 @@ def fuzz_campaign(fuzzer_args, schedulerConfig: SchedulerConfig,
                   maxMessages: Optional[int] = None, randomizationStrategyCtor: Callable[[], object] = FullyRandom,
                   computeProvenance: bool = True, violationWereLookingFor: Callable[[ViolationFingerprint], bool] = lambda f: True,
                   executions_per_test: int = 64, max_tests: int = 1024, tests_per_launch: int = 256, test_seed_base: int = 0,
-                  provenance_device: Optional[int] = 0, device: int = 0, p_max: int = 64, specialize: bool = False, ctx=None
+                  provenance_device: Optional[int] = 0, device: int = 0, p_max: int = 64, specialize: bool = False, ctx=None,
+                  in_flight: Optional[int] = None
                   ) -> Optional[Tuple[EventTrace, ViolationFingerprint, np.ndarray, np.ndarray]]:
     """fuzz() with the test axis on the device: what fuzz(lambda i: generate_fuzz_test(.., seed = test_seed_base + i), ..) returns
     for the same executions_per_test and max_tests - (trace, violation, initialTrace, filtered) or None - found by launches of
@@ -102,7 +103,9 @@ def fuzz_campaign(fuzzer_args, schedulerConfig: SchedulerConfig,
     path (RandomScheduler.explore's own last step) for its EventTrace; replay validation, violationWereLookingFor and the
     provenance pruning are fuzz()'s, and a test they reject sends the campaign on from the test after it.  When an execution
     before the reported one was aborted on a capacity, the campaign goes on with the largest pending set (fuzz() decides such an
-    execution alone with it; verdicts without an overflow do not depend on p_max); CapacityExceeded if that does not suffice."""
+    execution alone with it; verdicts without an overflow do not depend on p_max); CapacityExceeded if that does not suffice.
+    in_flight: 1..3 launches of every campaign call on the device at a time (demi_fuzz_campaign_pipelined; 0 = 2) - the same
+    answer; None, the default, is the synchronous entry point."""
     from . import _native
     from .capacity import CapacityExceeded, is_largest, largest
     from .schedulers import SrcDstFIFO
@@ -131,7 +134,7 @@ def fuzz_campaign(fuzzer_args, schedulerConfig: SchedulerConfig,
             res, fuzzTest, *found_areas = ctx.fuzz_campaign(num_events, weights, send_gen, prefix, lim, postfix=postfix,
                                                             executions_per_test=executions_per_test, tests_per_launch=tests_per_launch,
                                                             max_tests=max_tests - start, test_seed_base=test_seed_base + start,
-                                                            exec_seed_base=exec_seed_base)
+                                                            exec_seed_base=exec_seed_base, in_flight=in_flight)
             areas = found_areas[0] if with_fields else None
             if res.capacity_aborts:
                 # an execution aborted on a capacity has no verdict.  fuzz() decides it alone with the largest pending set; a verdict

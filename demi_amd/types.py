@@ -206,6 +206,22 @@ class FuzzCampaignResult(C.Structure):
                 ("verdict", Verdict)]
 
 
+class FuzzSummary(C.Structure):
+    """demi_fuzz_summary"""
+    _fields_ = [("first_hit", C.c_uint32), ("capacity_aborts", C.c_uint32), ("exec_index", C.c_uint32), ("aborted_before", C.c_uint32),
+                ("n_events", C.c_uint32), ("reserved", C.c_uint32), ("verdict", Verdict)]
+
+
+class FuzzPipelineParams(C.Structure):
+    """demi_fuzz_pipeline_params"""
+    _fields_ = [("in_flight", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class FuzzPipelineStats(C.Structure):
+    """demi_fuzz_pipeline_stats"""
+    _fields_ = [("launches_submitted", C.c_uint32), ("launches_discarded", C.c_uint32)]
+
+
 class RandomDdminParams(C.Structure):
     """demi_random_ddmin_params"""
     _fields_ = [("executions", C.c_uint32), ("depth", C.c_uint32), ("max_candidates", C.c_uint32), ("check_unmodified", C.c_uint32),

@@ -1284,6 +1284,48 @@ int demi_fuzz_campaign_fields(demi_ctx* ctx, const demi_fuzz_params* params, con
                               demi_ext_event* out_events /* [cap] */, uint64_t* out_areas /* [cap] */, uint32_t cap,
                               demi_fuzz_campaign_result* result);
 
+/* ---------------------------------------------------------- fuzz launches reduced on the device, campaigns with launches in flight
+ * What the loop of demi_fuzz_campaign computes from one launch's flag words and the violating test's verdict row, computed by
+ * kernels behind the launch (csrc/k_fuzz_reduce.hpp) - the host reads this record instead of 4 bytes per test: */
+typedef struct {
+  uint32_t first_hit;        /* lowest test index whose flag has bit 0; n_tests when none */
+  uint32_t capacity_aborts;  /* tests BELOW first_hit with bit 1 and without bit 0 */
+  uint32_t exec_index;       /* lowest violating execution of test first_hit; `executions` when none */
+  uint32_t aborted_before;   /* 1: an execution of first_hit below exec_index has DEMI_V_PENDING_OVF | DEMI_V_QUEUE_OVF */
+  uint32_t n_events;         /* n_ev of test first_hit (0 without a hit, and when the arrays were the caller's) */
+  uint32_t reserved;
+  demi_verdict verdict;      /* of (first_hit, exec_index); zero without a hit */
+} demi_fuzz_summary;         /* 40 bytes */
+/* flags == verdicts == NULL: the summary of the results the context's last demi_random_explore_tests / _areas call with
+ * tests == NULL left on the device (n_tests and executions as in that call; DEMI_ERR_NO_TRACE when there is none, or when the
+ * context has launched or loaded anything since) - a host of that entry point passes out_verdicts = out_flags =
+ * NULL there and reads this record.  flags [n_tests] and verdicts [n_tests][executions] both given: they are uploaded and
+ * reduced (n_events is 0).  One without the other: DEMI_ERR_INVALID_ARG.  At most 2^20 tests, 65536 executions per test, 2^28
+ * executions.  A flagged test whose row holds no violating verdict: DEMI_ERR_DEVICE. */
+int demi_fuzz_launch_summary(demi_ctx* ctx, const uint32_t* flags /* [n_tests] or NULL */,
+                             const demi_verdict* verdicts /* [n_tests][executions] or NULL */, uint32_t n_tests, uint32_t executions,
+                             demi_fuzz_summary* out);
+/* The test first_hit of the last demi_fuzz_launch_summary of resident results: its n_events events, and its payload areas (zeros
+ * when the resident tests have none; out_areas may be NULL).  Nothing is written when that summary had no hit.  DEMI_ERR_CAPACITY,
+ * with the length, when cap is smaller than n_events. */
+int demi_fuzz_launch_summary_row(demi_ctx* ctx, demi_ext_event* out_events /* [cap] */, uint64_t* out_areas /* [cap] or NULL */, uint32_t cap);
+
+/* demi_fuzz_campaign (field_gen == NULL: params->gen generates) / demi_fuzz_campaign_fields with up to in_flight launches on the
+ * device at a time: launch k + 1 is generated while launch k explores, its exploration is queued behind its own generation on the
+ * other of the context's two streams, and the host reads one demi_fuzz_summary per launch from pinned memory.  result, out_events
+ * and out_areas are byte for byte what the synchronous entry point returns for the same arguments, every refusal of it applies
+ * with the same message, and launches / tests_run / capacity_aborts count the launches up to the one that holds the first
+ * violating test.  The launches speculated behind that one are waited for and nothing is read from them:
+ * stats->launches_discarded (0 with in_flight == 1).  Every exit path, an error and DEMI_ERR_CAPACITY for a small `cap` included,
+ * waits for every launch it submitted; the context then holds no resident tests and takes any other call.  in_flight > 3:
+ * DEMI_ERR_INVALID_ARG.  Each launch in flight owns a set of buffers of the size of one launch. */
+typedef struct { uint32_t in_flight; /* 1..3 launches; 0 = 2 */ uint32_t reserved; } demi_fuzz_pipeline_params;
+typedef struct { uint32_t launches_submitted, launches_discarded; } demi_fuzz_pipeline_stats;
+int demi_fuzz_campaign_pipelined(demi_ctx* ctx, const demi_fuzz_params* params, const demi_fuzz_field_gen* field_gen /* NULL: the two-field generator */,
+                                 const demi_fuzz_campaign_params* campaign, const demi_fuzz_pipeline_params* pipeline,
+                                 const demi_limits* limits, demi_ext_event* out_events /* [cap] */, uint64_t* out_areas /* [cap], may be NULL */,
+                                 uint32_t cap, demi_fuzz_campaign_result* result, demi_fuzz_pipeline_stats* stats /* may be NULL */);
+
 /* ---------------------------------------------------------- measurement helpers (no reference counterpart)
  * Used by bench.py and the profiling scripts so that the figures beside the throughput are measured on the box that
  * prints them: the shader clock under load (s_memtime cycles per 100 MHz wall_clock64 tick) and the cycles one SIMD spends

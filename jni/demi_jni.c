@@ -1098,3 +1098,87 @@ JNIEXPORT jint JNICALL FN(fuzzCampaignFields)(JNIEnv* e, jclass c, jlong h, jint
   SET_LONGS(result, 9, o);
   return rc;
 }
+
+/* ---- a launch reduced on the device, campaigns with launches in flight (demi_fuzz_launch_summary / _row, demi_fuzz_campaign_pipelined) */
+/* flagsOrNull: int[nTests] with verdictsOrNull: long[2 * nTests * executions], or both null (the resident results); result: long[8] =
+ * first_hit, capacity_aborts, exec_index, aborted_before, n_events, 0, the verdict's flags | fingerprint << 32, its hash; eventsOrNull:
+ * byte[8 * 255], areasOrNull: long[255] (the violating test of the resident form) */
+JNIEXPORT jint JNICALL FN(fuzzLaunchSummary)(JNIEnv* e, jclass c, jlong h, jintArray flagsOrNull, jlongArray verdictsOrNull, jint nTests,
+                                            jint executions, jbyteArray eventsOrNull, jlongArray areasOrNull, jlongArray result) {
+  demi_fuzz_summary s;
+  jlong o[8];
+  (void)c;
+  if (nTests < 0 || executions < 0 || LEN(result) != 8 || (flagsOrNull == NULL) != (verdictsOrNull == NULL) ||
+      (flagsOrNull && (LEN(flagsOrNull) < nTests || LEN(verdictsOrNull) < 2 * (int64_t)nTests * (int64_t)executions)) ||
+      (eventsOrNull && LEN(eventsOrNull) < 8 * DEMI_MAX_EXT_EVENTS) || (areasOrNull && (!eventsOrNull || LEN(areasOrNull) < DEMI_MAX_EXT_EVENTS)))
+    return DEMI_ERR_INVALID_ARG;
+  void* fl = INTS(flagsOrNull);
+  void* v = LONGS(verdictsOrNull);
+  jint rc = (LOST(flagsOrNull, fl) || LOST(verdictsOrNull, v)) ? DEMI_ERR_INVALID_ARG
+            : demi_fuzz_launch_summary(CTX(h), (const uint32_t*)fl, (const demi_verdict*)v, (uint32_t)nTests, (uint32_t)executions, &s);
+  PUT_LONGS(verdictsOrNull, v, JNI_ABORT);
+  PUT_INTS(flagsOrNull, fl, JNI_ABORT);
+  if (rc) return rc;
+  if (eventsOrNull && !flagsOrNull) {
+    void* ev = BYTES(eventsOrNull);
+    void* ar = LONGS(areasOrNull);
+    rc = (LOST(eventsOrNull, ev) || LOST(areasOrNull, ar)) ? DEMI_ERR_INVALID_ARG
+         : demi_fuzz_launch_summary_row(CTX(h), (demi_ext_event*)ev, (uint64_t*)ar, DEMI_MAX_EXT_EVENTS);
+    PUT_LONGS(areasOrNull, ar, 0);
+    PUT_BYTES(eventsOrNull, ev, 0);
+    if (rc) return rc;
+  }
+  o[0] = (jlong)s.first_hit; o[1] = (jlong)s.capacity_aborts; o[2] = (jlong)s.exec_index; o[3] = (jlong)s.aborted_before; o[4] = (jlong)s.n_events;
+  o[5] = 0; o[6] = (jlong)((uint64_t)s.verdict.flags | ((uint64_t)s.verdict.fingerprint << 32)); o[7] = (jlong)s.verdict.hash;
+  SET_LONGS(result, 8, o);
+  return rc;
+}
+
+/* fuzzCampaign (genOrNull: byte[136]) or fuzzCampaignFields (fieldGenOrNull: byte[296], areasOrNull: long[255]) - exactly one generator -
+ * with inFlight launches on the device at a time; statsOrNull: long[2] = launches_submitted, launches_discarded */
+JNIEXPORT jint JNICALL FN(fuzzCampaignPipelined)(JNIEnv* e, jclass c, jlong h, jint numEvents, jbyteArray prefix, jbyteArray postfixOrNull,
+                                                jlongArray weightBits, jbyteArray genOrNull, jbyteArray fieldGenOrNull, jlongArray campaign,
+                                                jint inFlight, jintArray limits, jbyteArray events, jlongArray areasOrNull, jlongArray result,
+                                                jlongArray statsOrNull) {
+  jni_fuzzer f;
+  demi_fuzz_field_gen g;
+  demi_limits lim;
+  demi_fuzz_campaign_params cp;
+  demi_fuzz_pipeline_params pp;
+  demi_fuzz_campaign_result res;
+  demi_fuzz_pipeline_stats st;
+  jlong o[9], so[2];
+  (void)c;
+  if ((genOrNull == NULL) == (fieldGenOrNull == NULL) || inFlight < 0 || fuzzer_of(e, numEvents, prefix, postfixOrNull, weightBits, genOrNull, &f) ||
+      (fieldGenOrNull && field_gen_of(e, fieldGenOrNull, &g)) || limits_of(e, limits, &lim) || LEN(campaign) != 5 || LEN(result) != 9 || !events ||
+      LEN(events) < 8 * DEMI_MAX_EXT_EVENTS || (areasOrNull && LEN(areasOrNull) < DEMI_MAX_EXT_EVENTS) || (statsOrNull && LEN(statsOrNull) != 2))
+    return DEMI_ERR_INVALID_ARG;
+  memset(&cp, 0, sizeof cp);
+  memset(&pp, 0, sizeof pp);
+  pp.in_flight = (uint32_t)inFlight;
+  {
+    void* cb = LONGS(campaign);
+    if (LOST(campaign, cb)) return DEMI_ERR_INVALID_ARG;
+    const jlong* q = (const jlong*)cb;
+    cp.test_seed_base = (uint64_t)q[0]; cp.exec_seed_base = (uint64_t)q[1]; cp.executions_per_test = (uint32_t)q[2];
+    cp.tests_per_launch = (uint32_t)q[3]; cp.max_tests = (uint32_t)q[4];
+    PUT_LONGS(campaign, cb, JNI_ABORT);
+  }
+  void* ev = BYTES(events);
+  void* ar = LONGS(areasOrNull);
+  jint rc = (LOST(events, ev) || LOST(areasOrNull, ar)) ? DEMI_ERR_INVALID_ARG
+            : demi_fuzz_campaign_pipelined(CTX(h), &f.par, fieldGenOrNull ? &g : NULL, &cp, &pp, &lim, (demi_ext_event*)ev, (uint64_t*)ar,
+                                           DEMI_MAX_EXT_EVENTS, &res, &st);
+  PUT_LONGS(areasOrNull, ar, 0);
+  PUT_BYTES(events, ev, 0);
+  if (rc) return rc;
+  o[0] = (jlong)res.found; o[1] = (jlong)res.test_index; o[2] = (jlong)res.exec_index; o[3] = (jlong)res.n_events; o[4] = (jlong)res.tests_run;
+  o[5] = (jlong)res.launches; o[6] = (jlong)res.capacity_aborts;
+  o[7] = (jlong)((uint64_t)res.verdict.flags | ((uint64_t)res.verdict.fingerprint << 32)); o[8] = (jlong)res.verdict.hash;
+  SET_LONGS(result, 9, o);
+  if (statsOrNull) {
+    so[0] = (jlong)st.launches_submitted; so[1] = (jlong)st.launches_discarded;
+    SET_LONGS(statsOrNull, 2, so);
+  }
+  return rc;
+}

@@ -88,6 +88,20 @@ object DemiGpu {
   @native def fuzzCampaignFields(h: Long, numEvents: Int, prefix: Array[Byte], postfixOrNull: Array[Byte], weightBits: Array[Long],
                                  fieldGen: Array[Byte], campaign: Array[Long], limits: Array[Int], events: Array[Byte], areas: Array[Long],
                                  result: Array[Long]): Int
+  /** One launch reduced on the device (demi_fuzz_launch_summary, then demi_fuzz_launch_summary_row): flagsOrNull = int[nTests] with
+   *  verdictsOrNull = long[2 * nTests * executions], or both null for the results the last randomExploreTests(testsOrNull = null) left
+   *  in the context - that call then takes verdictsOrNull = null and this one is read instead of its flags.  result = long[8] (first_hit,
+   *  capacity_aborts, exec_index, aborted_before, n_events, 0, verdict flags | fingerprint << 32, verdict hash); eventsOrNull = byte[8 * 255]
+   *  and areasOrNull = long[255] receive the violating test of the resident form. */
+  @native def fuzzLaunchSummary(h: Long, flagsOrNull: Array[Int], verdictsOrNull: Array[Long], nTests: Int, executions: Int,
+                                eventsOrNull: Array[Byte], areasOrNull: Array[Long], result: Array[Long]): Int
+  /** fuzzCampaign / fuzzCampaignFields with up to inFlight launches on the device at a time (demi_fuzz_campaign_pipelined; inFlight 1..3,
+   *  0 = 2): exactly one of gen (byte[136]) and fieldGen (byte[296]) is non-null; areasOrNull = long[255] with fieldGen; result as
+   *  fuzzCampaign's; statsOrNull = long[2] (launches_submitted, launches_discarded).  The same answers as the synchronous calls. */
+  @native def fuzzCampaignPipelined(h: Long, numEvents: Int, prefix: Array[Byte], postfixOrNull: Array[Byte], weightBits: Array[Long],
+                                    genOrNull: Array[Byte], fieldGenOrNull: Array[Byte], campaign: Array[Long], inFlight: Int,
+                                    limits: Array[Int], events: Array[Byte], areasOrNull: Array[Long], result: Array[Long],
+                                    statsOrNull: Array[Long]): Int
   @native def replayGetKept(h: Long, maskOrNull: Array[Long], skip: Int, limits: Array[Int], verdict: Array[Long], kept: Array[Byte]): Int
   /** one round of STSSchedMinimizer.minimize, reduced on the device (demi_replay_removal_round): skip = the strategy's upcoming proposals,
    *  kept = byte[n recorded] (the executed-trace marks of proposal first_hit), result = long[6] (first_hit or -1, n_kept, retried, launches,
