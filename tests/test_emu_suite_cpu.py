@@ -154,6 +154,7 @@ def test_k3_and_provenance_sources_against_the_oracle_on_the_cpu():
                   "test_k3_gpu.py::test_reference_order_when_the_speculations_table_is_full",
                   "test_k3_gpu.py::test_checkpointed_interleavings_are_the_same_interleavings",
                   "test_k3_gpu.py::test_device_queue_edge_cases_against_the_host_bookkeeping",
+                  "test_k3_routes_gpu.py",
                   "test_provenance_gpu.py"], threads=1)
 
 
