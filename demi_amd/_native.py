@@ -24,7 +24,8 @@ EXPORTS = ["demi_ctx_create", "demi_ctx_destroy", "demi_last_error", "demi_versi
            "demi_fuzz_generate_fields", "demi_random_explore_tests_areas", "demi_fuzz_campaign_fields",
            "demi_fuzz_launch_summary", "demi_fuzz_launch_summary_row", "demi_fuzz_campaign_pipelined",
            "demi_replay_removal_round", "demi_minimize_internals", "demi_replay_wildcard_round", "demi_minimize_wildcards",
-           "demi_replay_batch_submit", "demi_replay_batch_wait"]
+           "demi_replay_batch_submit", "demi_replay_batch_wait",
+           "demi_dpor_wildcard_batch", "demi_wildcard_dpor_test"]
 
 _lib = None
 ALLGATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t)     # demi_allgather_fn
@@ -117,6 +118,10 @@ def lib():
     L.demi_dpor_load.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
     L.demi_dpor_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64, C.POINTER(T.DporParams),
                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.demi_dpor_wildcard_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64, C.POINTER(T.DporParams), C.c_uint32,
+                                           C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.demi_wildcard_dpor_test.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(T.DporParams), C.POINTER(T.WcdporParams),
+                                          C.c_void_p, C.POINTER(T.WcdporResult)]
     L.demi_dpor_explore.argtypes = [C.c_void_p, C.POINTER(T.DporParams), C.POINTER(T.DporSearch), C.c_void_p, C.c_void_p,
                                     C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(T.DporStats)]
     L.demi_random_explore_candidates.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(T.Limits), C.c_void_p, C.c_void_p]
@@ -818,6 +823,46 @@ class Context:
                                               verdicts.ctypes.data, traces.ctypes.data, tl.ctypes.data,
                                               pairs.ctypes.data, npairs.ctypes.data))
         return verdicts, [traces[i, :tl[i]].copy() for i in range(n)], [pairs[i, :npairs[i]].copy() for i in range(n)]
+
+    def dpor_wildcard_batch(self, prefixes, params, stop_after_next_trace=True, max_alts=64):
+        """One interleaving per next trace whose entries may be wildcards (demi_dpor_wildcard_batch; kinds DPOR_KIND_WILDCARD /
+        DPOR_KIND_EXACT_WORD of types.py).  Returns (verdicts, [trace arrays], [sorted ignored positions], [sorted trace indices
+        delivered by a wildcard], [DPOR_WILD_ALT_DTYPE arrays])."""
+        import numpy as np
+        n = len(prefixes)
+        stride = max([len(p) for p in prefixes] + [1])
+        pf = np.zeros((n, stride), dtype=T.DPOR_TRACE_DTYPE)
+        pl = np.zeros(n, dtype=np.uint32)
+        for i, p in enumerate(prefixes):
+            pf[i, :len(p)] = p
+            pl[i] = len(p)
+        verdicts = np.zeros(n, dtype=T.VERDICT_DTYPE)
+        traces = np.zeros((n, T.DPOR_MAX_TRACE), dtype=T.DPOR_TRACE_DTYPE)
+        tl = np.zeros(n, dtype=np.uint32)
+        ig = np.zeros((n, 4), dtype=np.uint64)
+        wc = np.zeros((n, 4), dtype=np.uint64)
+        alts = np.zeros((n, max(1, max_alts)), dtype=T.DPOR_WILD_ALT_DTYPE)
+        na = np.zeros(n, dtype=np.uint32)
+        self._check(lib().demi_dpor_wildcard_batch(self._h, pf.ctypes.data, pl.ctypes.data, stride, n, C.byref(params),
+                                                   1 if stop_after_next_trace else 0, max_alts, verdicts.ctypes.data, traces.ctypes.data,
+                                                   tl.ctypes.data, ig.ctypes.data, wc.ctypes.data, alts.ctypes.data, na.ctypes.data))
+        bits = lambda row: [64 * q + b for q in range(4) for b in range(64) if (int(row[q]) >> b) & 1]
+        return (verdicts, [traces[i, :tl[i]].copy() for i in range(n)], [bits(ig[i]) for i in range(n)], [bits(wc[i]) for i in range(n)],
+                [alts[i, :na[i]].copy() for i in range(n)])
+
+    def wildcard_dpor_test(self, initial, params, dpor_budget=0, batch=1, max_alts=0):
+        """WildcardMinimizer.testWithDpor of one proposal (demi_wildcard_dpor_test): (the hit's executed trace or None, its sorted
+        ignored positions, WcdporResult)."""
+        import numpy as np
+        init = np.ascontiguousarray(initial, dtype=T.DPOR_TRACE_DTYPE)
+        out = np.zeros(T.DPOR_MAX_TRACE, dtype=T.DPOR_TRACE_DTYPE)
+        wc = T.WcdporParams(dpor_budget, batch, max_alts, 0)
+        res = T.WcdporResult()
+        self._check(lib().demi_wildcard_dpor_test(self._h, init.ctypes.data if len(init) else None, len(init), C.byref(params), C.byref(wc),
+                                                  out.ctypes.data, C.byref(res)))
+        if not res.hit:
+            return None, [], res
+        return out[:res.trace_len].copy(), [64 * q + b for q in range(4) for b in range(64) if (int(res.ignored[q]) >> b) & 1], res
 
     def dpor_set_traces(self, original_trace=None, initial_trace=None):
         """ArvindDistanceOrdering.init(sched, originalTrace) and DPORwHeuristics.setInitialTrace for the following dpor_explore

@@ -244,6 +244,7 @@ __device__ inline uint32_t k3_racing_pairs(const demi_dpor_trace_entry* __restri
   return total;
 }
 
+#ifndef DEMI_K3_DECLS_ONLY   // (k3_wildcard.hpp's module takes the declarations above and none of the kernels)
 __global__ __launch_bounds__(K3_WAVES * 64) void k3_dpor(const K3Args args) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   Tables t;
@@ -743,8 +744,9 @@ __global__ __launch_bounds__(K3_WAVES * 64) void k3_dpor(const K3Args args) {
 #endif
 #undef TIMER_BIT
 }
+#endif
 
-#ifndef __HIPCC_RTC__      // (a generic kernel of the library: nothing in it depends on the table)
+#if !defined(__HIPCC_RTC__) && !defined(DEMI_K3_DECLS_ONLY)      // (a generic kernel of the library: nothing in it depends on the table)
 // dpor()'s pair loop for the n interleavings k3_dpor just finished: one wave per trace, every trace of the round at once (a
 // 16 384-interleaving round is sixteen waves per SIMD: the analysis' dependent LDS reads hide behind one another instead of
 // holding up a wave's simulators).  Writes pairs[s][..] and n_pairs[s], and DEMI_V_PAIRS_OVF into the verdict.

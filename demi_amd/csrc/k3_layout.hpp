@@ -44,6 +44,15 @@ inline BatchLayout batch_area(uint64_t n, uint32_t stride, uint32_t max_pairs) {
           c.take(4 * n), c.take(kPair * (size_t)max_pairs * n), c.take(4 * n), c.take(4 * n), c.at};
 }
 
+// demi_dpor_wildcard_batch / demi_wildcard_dpor_test (ctx->d_dpor): prefixes, their lengths, verdicts, traces, trace lengths,
+// the ignored-position and picked-by-wildcard masks (256 bits each per interleaving), the alternative records and their counts
+struct WildBatchLayout { size_t o_pfx, o_pl, o_v, o_t, o_tl, o_ig, o_wc, o_al, o_na, total; };
+inline WildBatchLayout wild_batch_area(uint64_t n, uint32_t stride, uint32_t max_alts) {
+  Carve c;
+  return {c.take(kEntry * (size_t)stride * n), c.take(4 * n), c.take(kVerdict * n), c.take(kEntry * DEMI_DPOR_MAX_TRACE * n),
+          c.take(4 * n), c.take(32 * n), c.take(32 * n), c.take(sizeof(demi_dpor_wild_alt) * (size_t)max_alts * n), c.take(4 * n), c.at};
+}
+
 // A round of the resident exploration (ctx->d_res): items, verdicts, pair counts, pairs, the flipped pairs' slots, decided
 // points, kills, counters - so far also what a launch of the REFERENCE order reads (round_ref_begin: items, pairs, pair
 // counts, verdicts, counters) - and behind them the parent filter's survivors and their counts.

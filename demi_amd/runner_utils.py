@@ -290,11 +290,12 @@ class _WildcardSpeculativeDDMin(SpeculativeDDMin):
 def run_the_gamut(schedulerConfig: SchedulerConfig, trace: EventTrace, violation: ViolationFingerprint,
                   stages: Sequence[str] = ("DDMin", "IntMin"), device: int = 0, p_max: int = 64,
                   shouldRerunDDMin: Callable[[np.ndarray], bool] = lambda externals: True, native_intmin: bool = False,
-                  native_wildcards: bool = False):
+                  native_wildcards: bool = False, dpor_budget: int = 256):
     """The stages of RunnerUtils.runTheGamut (:165-380) that run on the GPU path, in the reference's order:
     stsSchedDDMin (external events), then minimizeInternals with LeftToRightOneAtATime, then - only when named in `stages` -
     "WildCardDDMinNoBacktracks" and "WildCardDDMinLastOnly" (wildcardDDMin over the current trace, :363-411, guarded by
-    shouldRerunDDMin as there), then "WildcardsNoBackTracks" and "WildcardsLastOnly" (wildcard_minimization.WildcardMinimizer, ClockClusterizer).  Returns a dict with the MCS
+    shouldRerunDDMin as there), then "WildcardsNoBackTracks" and "WildcardsLastOnly" (wildcard_minimization.WildcardMinimizer, ClockClusterizer),
+    then "Wildcards" (the same with DPORwHeuristics as the oracle, dpor_budget interleavings per proposal).  Returns a dict with the MCS
     (indices into trace.original_externals), the verified MCS execution, the internally minimized execution and the
     replay counts of each stage.  native_intmin: the internal minimization as one native call (demi_minimize_internals); native_wildcards: each
     wildcard stage likewise (demi_minimize_wildcards)."""
@@ -345,4 +346,15 @@ def run_the_gamut(schedulerConfig: SchedulerConfig, trace: EventTrace, violation
                                                device=device, p_max=p_max, native=native_wildcards).minimize()
             out.setdefault("wildcard_replays", {})[stage] = stats.total_replays
             out.update(wildcard_minimized=cur_trace, wildcard_deliveries=countMsgEvents(cur_trace))
+    # "Wildcards" (RunnerUtils.scala:441-454), opt-in: the same minimizer with fungClocksScheduler = DPORwHeuristics as its oracle -
+    # the default resolution strategy's backtrack points are explored (wildcard_minimization.DporWildcardOracle).  The
+    # reference's timeBudgetSeconds is dpor_budget here, interleavings per proposal.
+    if "Wildcards" in stages and cur_trace is not None:
+        from . import wildcard_minimization as W
+        stats = MinimizationStats()
+        _, cur_trace = W.WildcardMinimizer(schedulerConfig, cur_trace.original_externals, cur_trace, violation, stats=stats,
+                                           testScheduler=W.TestScheduler.DPORwHeuristics, dpor_budget=dpor_budget,
+                                           device=device, p_max=p_max).minimize()
+        out.setdefault("wildcard_replays", {})["Wildcards"] = stats.total_replays
+        out.update(wildcard_minimized=cur_trace, wildcard_deliveries=countMsgEvents(cur_trace))
     return out

@@ -58,6 +58,7 @@ V_DIVERGED = 0x10
 V_TRACE_OVF = 0x20
 V_PAIRS_OVF = 0x40
 V_SELFMSG = 0x80
+V_ALTS_OVF = 0x100        # K3W: more alternatives than max_alts (aborted)
 DPOR_MAX_TRACE = 256
 DPOR_ROOT_KEY = 0xCBF29CE484222325
 DPOR_PRIME = 0x100000001B3
@@ -137,6 +138,13 @@ FILTER_ABSENTS_OFF, FILTER_ABSENTS_LITERAL, FILTER_ABSENTS_CORRECTED = 0, 1, 2  
 WILDCARD_HEAD, WILDCARD_FIRST, WILDCARD_LAST = 0, 1, 2     # demi_wildcard_policy
 WC_REPRODUCES, WC_UNKNOWN, WC_LONGER = 1, 2, 4             # demi_wildcard_candidate.flags (DEMI_WC_*)
 NO_HIT = 0xFFFFFFFF                                        # first_hit / first_ovf: none
+WILDCARD_BACKTRACK_NONE, WILDCARD_BACKTRACK_ALL, WILDCARD_BACKTRACK_LAST_DISTINCT = 0, 1, 2     # demi_wildcard_backtrack
+DPOR_KIND_ROOT, DPOR_KIND_DELIVERY, DPOR_KIND_MARKER, DPOR_KIND_WILDCARD, DPOR_KIND_EXACT_WORD = range(5)   # demi_dpor_trace_entry.kind
+
+
+def wildcard_selector_key(types, policy, backtrack):
+    """The key of a DPOR_KIND_WILDCARD next-trace entry (include/demi_gpu.h)."""
+    return (int(types) & 0xFFFFFFFF) | (int(policy) & 0xFF) << 32 | (int(backtrack) & 0xFF) << 40
 
 
 class Limits(C.Structure):
@@ -324,6 +332,18 @@ class DporParams(C.Structure):
                 ("prioritize_pending", C.c_uint32)]
 
 
+class WcdporParams(C.Structure):
+    """demi_wcdpor_params"""
+    _fields_ = [("dpor_budget", C.c_uint32), ("batch", C.c_uint32), ("max_alts", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class WcdporResult(C.Structure):
+    """demi_wcdpor_result"""
+    _fields_ = [("hit", C.c_uint32), ("interleavings", C.c_uint32), ("speculated", C.c_uint32), ("launches", C.c_uint32),
+                ("exhausted", C.c_uint32), ("budget_reached", C.c_uint32), ("retried", C.c_uint32), ("trace_len", C.c_uint32),
+                ("skipped_explored", C.c_uint32), ("points", C.c_uint32), ("reserved", C.c_uint32 * 2), ("ignored", C.c_uint64 * 4)]
+
+
 class DporSearch(C.Structure):
     _fields_ = [("batch", C.c_uint32), ("max_interleavings", C.c_uint32), ("stop_if_violation", C.c_uint32),
                 ("track_history", C.c_uint32), ("order", C.c_uint32), ("cache_mb", C.c_uint32),
@@ -383,7 +403,9 @@ def rec_events(a):
 DPOR_TRACE_DTYPE = np.dtype([("key", "<u8"), ("word", "<u4"), ("parent", "u1"), ("qperiod", "u1"), ("depth", "u1"),
                              ("kind", "u1")])
 DPOR_PAIR_DTYPE = np.dtype([("branch", "u1"), ("later", "u1"), ("earlier", "u1"), ("pad", "u1")])
+DPOR_WILD_ALT_DTYPE = np.dtype([("key", "<u8"), ("word", "<u4"), ("trace_len", "<u2"), ("next_pos", "u1"), ("parent", "u1")])
 assert DPOR_TRACE_DTYPE.itemsize == 16 and DPOR_PAIR_DTYPE.itemsize == 4
+assert DPOR_WILD_ALT_DTYPE.itemsize == 16
 VIOLATION_DTYPE = np.dtype([("index", "<u8"), ("fingerprint", "<u4"), ("flags", "<u4")])
 assert WILDCARD_CANDIDATE_DTYPE.itemsize == 24
 assert VERDICT_DTYPE.itemsize == 16 and VIOLATION_DTYPE.itemsize == 16 and EXT_EVENT_DTYPE.itemsize == 8 and REC_EVENT_DTYPE.itemsize == 16

@@ -32,6 +32,7 @@ class AmbiguityResolutionStrategy:
     """resolve(msgSelector, pending, backtrackSetter) -> index of the selected pending message, or None.  `policy` is what the
     device knows the strategy as."""
     policy = T.WILDCARD_FIRST
+    backtrack = T.WILDCARD_BACKTRACK_NONE      # which alternatives it hands to the backtrackSetter (DPORwHeuristics only)
 
     def resolve(self, msgSelector, pending: Sequence, backtrackSetter=None) -> Optional[int]:
         matching = [i for i, m in enumerate(pending) if msgSelector(m)]
@@ -47,11 +48,14 @@ class SrcDstFIFOOnly(AmbiguityResolutionStrategy):
 
 
 class BackTrackStrategy(AmbiguityResolutionStrategy):
-    """:45-77: the first match (the backtrack points it sets are no-ops under STSSched)."""
+    """:45-77: the first match (the backtrack points it sets are no-ops under STSSched; under DPORwHeuristics: one per later
+    match of another message value, youngest first)."""
+    backtrack = T.WILDCARD_BACKTRACK_ALL
 
 
 class FirstAndLastBacktrack(AmbiguityResolutionStrategy):
-    """:80-107: the first match."""
+    """:80-107: the first match (under DPORwHeuristics: one backtrack point, for the youngest match of another message value)."""
+    backtrack = T.WILDCARD_BACKTRACK_LAST_DISTINCT
 
 
 class LastOnlyStrategy(AmbiguityResolutionStrategy):
@@ -101,6 +105,16 @@ class Clusterizer:
     def selectors(self) -> Tuple[np.ndarray, np.ndarray]:
         """(type_sets uint32[n_rec], policies uint8[n_rec]) of the trace's records: what a kept delivery is wildcarded to."""
         raise NotImplementedError
+
+    def backtracks(self) -> np.ndarray:
+        """uint8[n_rec]: the demi_wildcard_backtrack of every record's wildcard (the resolution strategy's; the timer wildcard
+        of ClockClusterizer sets none)."""
+        ts, _ = self.selectors()
+        bt = np.where(ts != 0, self.resolutionStrategy.backtrack, T.WILDCARD_BACKTRACK_NONE).astype(np.uint8)
+        for i, inc, x in zip(self.d.idx, self.d.clock_inc, self.d.external):
+            if inc and not x and isinstance(self, ClockClusterizer):
+                bt[i] = T.WILDCARD_BACKTRACK_NONE
+        return bt
 
     def clone(self) -> "Clusterizer":
         import copy
@@ -405,6 +419,118 @@ class StsWildcardOracle:
         self._ctx.close()
 
 
+# ------------------------------------------------------------------ the DPOR oracle on the GPU
+class TestScheduler:
+    """WildcardMinimizer.scala's TestScheduler enumeration."""
+    STSSched, DPORwHeuristics = "STSSched", "DPORwHeuristics"
+
+
+def convertToEventTrace(model: Model, trace: np.ndarray, mcs: np.ndarray) -> np.ndarray:
+    """DPORwHeuristicsUtil.convertToEventTrace (DPORwHeuristics.scala:1246-1268) of an executed DPOR trace (DPOR_TRACE_DTYPE):
+    a Spawn record per Start of `mcs`, then MsgSend + MsgEvent per delivered entry, ids 1, 2, ... in order of appearance.
+    Pinned: the ext_idx of an external delivery is the Send that enqueued it - equal words from deadLetters to one receiver are
+    delivered in send order.  Tables whose message words fit a trace entry only (not DEMI_MODEL_WIDE)."""
+    if model.wide:
+        raise ValueError("convertToEventTrace: a trace entry of a DEMI_MODEL_WIDE table does not hold the whole payload area")
+    out = []
+    sends: Dict[Tuple[int, int, int, int], List[int]] = {}
+    for i, e in enumerate(mcs):
+        if int(e["kind"]) == T.EV_START:
+            out.append((T.REC_SPAWN, 0, int(e["a"]), 0, 0, 0, 0, i, 0, 0))
+        elif int(e["kind"]) == T.EV_SEND:
+            sends.setdefault((int(e["a"]), int(e["msg_type"]), int(e["p0"]), int(e["p1"])), []).append(i)
+    n = 0
+    for e in trace:
+        if int(e["kind"]) != T.DPOR_KIND_DELIVERY:
+            continue
+        w = int(e["word"])
+        mtype, rcv, snd, p0, p1 = w & 31, (w >> 5) & 7, (w >> 8) & 15, (w >> 16) & 255, w >> 24
+        n += 1
+        dead = snd == T.DEADLETTERS
+        external = dead and model.msg_class[mtype] == T.MSG_EXTERNAL
+        ext_idx = sends[(rcv, mtype, p0, p1)].pop(0) if external else 255
+        out.append((T.REC_MSG_SEND, snd, rcv, mtype, p0, p1, 1 if external else 2 if dead else 0, ext_idx, 0, n))
+        out.append((T.REC_MSG_EVENT, snd, rcv, mtype, p0, p1, 0, 255, 0, n))
+    return np.array(out, dtype=T.REC_EVENT_DTYPE) if out else np.zeros(0, dtype=T.REC_EVENT_DTYPE)
+
+
+class DporWildcardOracle:
+    """WildcardMinimizer.testWithDpor (WildcardMinimizer.scala:67-114) for the traces a Clusterizer proposes: one call of
+    demi_wildcard_dpor_test per proposal - K3 with wildcard entries (csrc/k3_wildcard.hpp) around the backtrack queue of
+    csrc/wcdpor_host.hpp.  A proposal is lowered to its UniqueMsgEvents: a wildcarded delivery to a DPOR_KIND_WILDCARD entry
+    (type set, policy, backtrack mode), the exact delivery of an external message to a DPOR_KIND_EXACT_WORD entry.
+    dpor_budget: interleavings per proposal (0 = unbounded); batch: queue heads per launch."""
+
+    def __init__(self, schedulerConfig: SchedulerConfig, device: int = 0, p_max: int = 64, dpor_budget: int = 256, batch: int = 64,
+                 max_alts: int = 0, specialize: bool = False):
+        if schedulerConfig.model is None or schedulerConfig.model.inv_kind == T.INV_NONE:
+            raise ValueError("Must invoke setInvariant before test()")
+        self.schedulerConfig = schedulerConfig
+        self.p_max, self.dpor_budget, self.batch, self.max_alts = p_max, dpor_budget, max(1, int(batch)), max_alts
+        self._ctx = _native.Context(device)
+        self._ctx.model_load(schedulerConfig.model.to_struct())
+        if specialize or getattr(schedulerConfig.model, "compiled_only", False):
+            self._ctx.model_specialize()
+        self._trace = None
+        self.launches = self.interleavings = self.speculated = 0
+        self.results: List[T.WcdporResult] = []
+
+    def load(self, trace: EventTrace, type_sets, policies, backtracks):
+        from .incremental_ddmin import _dpor_trace_indices, convertToDPORTrace
+        mcs = trace.original_externals
+        areas = None
+        if trace.ext_areas is not None and len(trace.ext_areas) == len(mcs):
+            areas = np.asarray(trace.ext_areas)[_dpor_trace_indices(mcs, False)]
+        self._ctx.dpor_load(convertToDPORTrace(mcs, ignoreQuiescence=False), areas=areas)
+        self._trace = trace
+        self._sel = (np.asarray(type_sets, dtype=np.uint32), np.asarray(policies, dtype=np.uint8), np.asarray(backtracks, dtype=np.uint8))
+
+    def present_records(self, present) -> List[int]:
+        """The proposal's UniqueMsgEvents, as record indices (what an ignored index counts in, WildcardMinimizer.scala:227-235)."""
+        ev = self._trace.events
+        return [int(i) for i in np.nonzero(ev["kind"] == T.REC_MSG_EVENT)[0] if present[int(i)]]
+
+    def lower(self, present) -> np.ndarray:
+        ev = self._trace.events
+        model = self.schedulerConfig.model
+        ts, po, bt = self._sel
+        recs = self.present_records(present)
+        out = np.zeros(len(recs), dtype=T.DPOR_TRACE_DTYPE)
+        for k, i in enumerate(recs):
+            snd, rcv = int(ev["snd"][i]), int(ev["rcv"][i])
+            if int(ts[i]):
+                out[k] = (T.wildcard_selector_key(ts[i], po[i], bt[i]), (rcv << 5) | (snd << 8), 0, 0, 0, T.DPOR_KIND_WILDCARD)
+            else:
+                area = int(ev["p0"][i]) | int(ev["p1"][i]) << 16 | int(ev["p_hi"][i]) << 32
+                head = int(ev["msg_type"][i]) | (rcv << 5) | (snd << 8)
+                w = head | area << 16 if model.wide else head | int(ev["p0"][i]) << 16 | int(ev["p1"][i]) << 24
+                out[k] = (w, w & 0xFFFFFFFF, 0, 0, 0, T.DPOR_KIND_EXACT_WORD)
+        return out
+
+    def test_raw(self, present, violation: ViolationFingerprint, dpor_budget=None, batch=None):
+        """(the hit's executed DPOR trace or None, its ignored positions, WcdporResult)."""
+        init = self.lower(present)
+        par = T.DporParams(0, len(init), 1, violation.code, self.p_max, 0, 1)
+        trace, ignored, res = self._ctx.wildcard_dpor_test(init, par, dpor_budget=self.dpor_budget if dpor_budget is None else dpor_budget,
+                                                           batch=self.batch if batch is None else batch, max_alts=self.max_alts)
+        self.launches += int(res.launches)
+        self.interleavings += int(res.interleavings)
+        self.speculated += int(res.speculated)
+        self.results.append(res)
+        return trace, ignored, res
+
+    def test(self, present, violation: ViolationFingerprint):
+        """testWithDpor: (EventTrace, ignored positions) iff an interleaving triggers the violation, else None."""
+        trace, ignored, _ = self.test_raw(present, violation)
+        if trace is None:
+            return None
+        mcs = self._trace.original_externals
+        return EventTrace(convertToEventTrace(self.schedulerConfig.model, trace, mcs), mcs, self._trace.ext_areas), ignored
+
+    def shutdown(self):
+        self._ctx.close()
+
+
 # ------------------------------------------------------------------ WildcardMinimizer.scala
 class ClusteringStrategy:
     ClockClusterizer, SingletonClusterizer, ClockThenSingleton = "ClockClusterizer", "SingletonClusterizer", "ClockThenSingleton"
@@ -419,7 +545,14 @@ class WildcardMinimizer:
     def __init__(self, schedulerConfig: SchedulerConfig, mcs: np.ndarray, trace: EventTrace, violation: ViolationFingerprint,
                  skipClockClusters: bool = False, resolutionStrategy: Optional[AmbiguityResolutionStrategy] = None,
                  clusteringStrategy: str = ClusteringStrategy.ClockClusterizer, stats: Optional[MinimizationStats] = None,
-                 max_batch: int = 1 << 14, oracle=None, device: int = 0, p_max: int = 64, native: bool = False):
+                 max_batch: int = 1 << 14, oracle=None, device: int = 0, p_max: int = 64, native: bool = False,
+                 testScheduler: str = TestScheduler.STSSched, dpor_budget: int = 256, batch: int = 64):
+        if testScheduler not in (TestScheduler.STSSched, TestScheduler.DPORwHeuristics):
+            raise ValueError("unknown test scheduler %r" % (testScheduler,))
+        if testScheduler == TestScheduler.DPORwHeuristics and native:
+            raise ValueError("native=True is demi_minimize_wildcards, the STSSched loop: not built for TestScheduler.DPORwHeuristics")
+        self.testScheduler, self.dpor_budget, self.batch = testScheduler, dpor_budget, batch
+        self.dropped_ignored = 0                       # DPOR branch: ignored indices with no proposal event behind them
         self.schedulerConfig = schedulerConfig
         self.native = native
         self.mcs = mcs
@@ -443,8 +576,13 @@ class WildcardMinimizer:
         model = self.schedulerConfig.model
         aggressiveness = Aggressiveness.STOP_IMMEDIATELY if self.skipClockClusters else Aggressiveness.ALL_TIMERS_FIRST_ITR
         own = self.oracle is None
-        if own:
+        dpor = self.testScheduler == TestScheduler.DPORwHeuristics
+        if own and dpor:
+            self.oracle = DporWildcardOracle(self.schedulerConfig, device=self._device, p_max=self._p_max, dpor_budget=self.dpor_budget,
+                                             batch=self.batch)
+        elif own:
             self.oracle = StsWildcardOracle(self.schedulerConfig, device=self._device, p_max=self._p_max)
+        doMinimize = self.doMinimizeDpor if dpor else self.doMinimize
         try:
             if self.native:
                 _, minTrace = self.oracle.minimize_native(self.mcs, self.trace, self.violation, self.clusteringStrategy,
@@ -459,9 +597,9 @@ class WildcardMinimizer:
                                                skipClockClusters=self.skipClockClusters)
             else:
                 clusterizer = SingletonClusterizer(self.trace, model, self.resolutionStrategy)
-            minTrace = self.doMinimize(clusterizer, self.trace)
+            minTrace = doMinimize(clusterizer, self.trace)
             if self.clusteringStrategy == ClusteringStrategy.ClockThenSingleton:
-                minTrace = self.doMinimize(SingletonClusterizer(minTrace, model, self.resolutionStrategy), minTrace)
+                minTrace = doMinimize(SingletonClusterizer(minTrace, model, self.resolutionStrategy), minTrace)
             if not self.skipClockClusters:
                 self.internal_sizes.append(countMsgEvents(minTrace))          # fencepost
             return self._stats, minTrace
@@ -514,6 +652,38 @@ class WildcardMinimizer:
             if len(ret.events) <= len(minTrace.events):
                 minTrace = ret
             last = (True, frozenset(id_of_rec[i] for i in ignoredAbsentIndices))
+        return minTrace
+
+
+    def doMinimizeDpor(self, clusterizer: Clusterizer, startTrace: EventTrace) -> EventTrace:
+        """doMinimize's DPORwHeuristics branch (:190-241): one testWithDpor per proposal; the proposals depend on each other's
+        outcome AND every one is an exploration of its own, so they are consulted one at a time."""
+        minTrace = startTrace
+        ev = startTrace.events
+        self.oracle.load(startTrace, *clusterizer.selectors(), clusterizer.backtracks())
+        nextTrace = clusterizer.getNextTrace(False, frozenset())
+        while nextTrace is not None:
+            self.proposals.append(nextTrace)
+            if not self.skipClockClusters:
+                self.internal_sizes.append(countMsgEvents(minTrace))
+            self._stats.increment_replays(1)            # (DPORwHeuristics.test counts one replay per call)
+            got = self.oracle.test(nextTrace, self.violation)
+            ignoredAbsentIds = set()
+            if got is not None:
+                ret, ignoredAbsentIndices = got
+                ret = EventTrace(ret.events, self.mcs, self.ext_areas)
+                if len(ret.events) <= len(minTrace.events):
+                    minTrace = ret
+                # (:227-235) the indices count in the proposal's UniqueMsgEvents; after a backtracked hit they are positions of
+                # the hitting interleaving's own next trace - as written.  Pinned: one with no event behind it is dropped
+                adjusted = self.oracle.present_records(nextTrace) if hasattr(self.oracle, "present_records") else \
+                    [int(i) for i in np.nonzero(ev["kind"] == T.REC_MSG_EVENT)[0] if nextTrace[int(i)]]
+                for i in ignoredAbsentIndices:
+                    if i < len(adjusted):
+                        ignoredAbsentIds.add(int(ev["id"][adjusted[i]]))
+                    else:
+                        self.dropped_ignored += 1
+            nextTrace = clusterizer.getNextTrace(got is not None, frozenset(ignoredAbsentIds))
         return minTrace
 
 

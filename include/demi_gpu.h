@@ -862,6 +862,83 @@ int demi_dpor_batch(demi_ctx* ctx, const demi_dpor_trace_entry* prefixes, const 
                     demi_dpor_trace_entry* out_traces, uint32_t* out_trace_len, demi_dpor_pair* out_pairs,
                     uint32_t* out_n_pairs);
 
+/* ---------------------------------------------------------- K3W: DPORwHeuristics as the oracle of the wildcard minimizer
+ * WildcardMinimizer with TestScheduler.DPORwHeuristics (WildcardMinimizer.scala:67-114, runTheGamut's "Wildcards" stage,
+ * RunnerUtils.scala:441-454): the next trace of an interleaving is a proposal's UniqueMsgEvents, and a wildcard that could
+ * have delivered another pending message sets a backtrack point for it (DPORwHeuristics.scala:474-514;
+ * AmbiguityResolutionStrategies.scala:44-107).  Two further kinds of next-trace entry exist for it (demi_dpor_trace_entry.kind):
+ *   3  a wildcard MsgEvent(snd, rcv, WildCardMatch): `word` holds only sender and receiver, in the table's layout; `key` is
+ *      type set (bits 0..31, bit t = message type t matches) | demi_wildcard_policy << 32 | demi_wildcard_backtrack << 40.
+ *      It is matched against ALL pending messages of (snd, rcv) in send order (:484) - HEAD: the oldest, if its type is in the
+ *      set; FIRST: the oldest whose type is; LAST: the youngest whose type is.
+ *   4  Unique(MsgEvent, id = -1) of an external message (equivalentTo's first case, :433-438): the oldest pending message whose
+ *      word equals `key` (the whole message word; 64 bits in a DEMI_MODEL_WIDE table); `word` is its low half.
+ * FIRST with a backtrack mode reports the later matches a backtrackSetter is called for: per message value (type and payload
+ * area) other than the first match's, the youngest pending message of that value, youngest first (ALL = BackTrackStrategy,
+ * :44-77) - or only the first of them (LAST_DISTINCT = FirstAndLastBacktrack, :80-107).                                       */
+#define DEMI_DPOR_KIND_WILDCARD   3
+#define DEMI_DPOR_KIND_EXACT_WORD 4
+typedef enum {
+  DEMI_WILDCARD_BACKTRACK_NONE = 0,
+  DEMI_WILDCARD_BACKTRACK_ALL = 1,
+  DEMI_WILDCARD_BACKTRACK_LAST_DISTINCT = 2
+} demi_wildcard_backtrack;
+/* one alternative: backTrack.enqueue((branchI, (priorEvent, toPlayNext), currentTrace.tail ++ toPlayNext ++ nextTrace)), :485-497.
+ * priorEvent is trace entry trace_len - 1, branchI the deepest common ancestor of that entry and of entry `parent` (parent
+ * links of the executed trace), the rest of the next trace starts behind position next_pos. */
+typedef struct {
+  uint64_t key;        /* node of toPlayNext */
+  uint32_t word;       /* its message word (low half in a wide table) */
+  uint16_t trace_len;  /* currentTrace.length when the wildcard was matched */
+  uint8_t next_pos;    /* position of the wildcard in the interleaving's next trace */
+  uint8_t parent;      /* trace index of the delivery that produced toPlayNext */
+} demi_dpor_wild_alt;  /* 16 bytes */
+#define DEMI_V_ALTS_OVF 0x100u /* more alternatives than max_alts: aborted (K3W verdicts carry no traceIdx in bits 8..15) */
+
+/* n interleavings in one launch.  prefixes as in demi_dpor_batch, kinds 3 and 4 included; stride <= 256.  params->max_pairs is
+ * ignored (skipBacktrackComputation, :1120).  stop_after_next_trace: stopAfterNextTrace (:588-590, 612-613).  Outputs: verdicts,
+ * traces and their lengths as demi_dpor_batch; out_ignored[i] = 256 bits, bit p set iff getNextMatchingMessage reported position
+ * p of next trace i as absent (ignoreAbsentCallback(origNextTraceSize - nextTrace.size), :542-555; only with
+ * params->prioritize_pending); out_wild[i] = 256 bits, bit k set iff entry k of trace i was delivered by a wildcard - the
+ * (trace[k - 1], trace[k]) the reference marks explored (:504-508); out_alts [n][max_alts] with out_n_alts[i] records in the
+ * order the backtrackSetter was called.  One record beyond max_alts aborts the interleaving with DEMI_V_ALTS_OVF; an aborted
+ * interleaving (any capacity) has trace length 0 and no records.
+ * Refused by name (DEMI_ERR_INVALID_ARG): a table of more than 8 actors; an attached communicator; stride > 256. */
+int demi_dpor_wildcard_batch(demi_ctx* ctx, const demi_dpor_trace_entry* prefixes, const uint32_t* prefix_len, uint32_t stride,
+                             uint64_t n, const demi_dpor_params* params, uint32_t stop_after_next_trace, uint32_t max_alts,
+                             demi_verdict* out_verdicts, demi_dpor_trace_entry* out_traces, uint32_t* out_trace_len,
+                             uint64_t* out_ignored /* [n][4] */, uint64_t* out_wild /* [n][4] */,
+                             demi_dpor_wild_alt* out_alts /* [n][max_alts] */, uint32_t* out_n_alts);
+
+/* WildcardMinimizer.testWithDpor of ONE proposal (WildcardMinimizer.scala:67-114) in one call: a fresh DPORwHeuristics with
+ * prioritizePendingUponDivergence, skipBacktrackComputation and stopAfterNextTrace runs `initial` (setInitialTrace, the
+ * proposal's uniques as kind 3 / 4 entries), then the backtrack points its wildcards set, highest branchI first and ties in
+ * creation order (DefaultBacktrackOrdering), skipping explored (priorEvent, toPlayNext) pairs (ExploredTacker over node keys),
+ * until an interleaving violates params->looking_for, the queue is empty, or the budget is spent.  params->max_messages is
+ * setMaxMessagesToSchedule (the caller passes n_initial), params->prioritize_pending is forced to 1.
+ *   dpor_budget  interleavings per call, 0 = unbounded: the reference's budgetSeconds as a COUNT.  The first interleaving always
+ *                runs; dpor() after interleaving number dpor_budget returns None.
+ *   batch        queue heads executed per launch (>= 1).  They are committed one at a time in the reference's order; the
+ *                children of a committed interleaving that outrank the remaining heads run before them.
+ *   max_alts     alternative records per interleaving (0 = 64).
+ * Result: hit (then out_trace[0 .. trace_len) is the reproducing interleaving's trace and `ignored` its absent positions),
+ * interleavings = what the one-at-a-time algorithm executed up to and including the hit (stats.increment_replays counts one
+ * per call; this is the number of start_trace calls), speculated = executed and discarded, exhausted / budget_reached = why a
+ * call without a hit ended.  An interleaving aborted on a capacity before the hit in commit order is no answer: it runs once
+ * more with p_max = DEMI_MAX_PENDING and max_alts = 256, then the call fails with DEMI_ERR_CAPACITY.
+ * Refused by name as demi_dpor_wildcard_batch. */
+typedef struct { uint32_t dpor_budget, batch, max_alts, reserved; } demi_wcdpor_params;
+typedef struct {
+  uint32_t hit, interleavings, speculated, launches, exhausted, budget_reached, retried, trace_len;
+  uint32_t skipped_explored;   /* backtrack points getNext dropped because their pair was explored */
+  uint32_t points;             /* backtrack points set */
+  uint32_t reserved[2];
+  uint64_t ignored[4];
+} demi_wcdpor_result;
+int demi_wildcard_dpor_test(demi_ctx* ctx, const demi_dpor_trace_entry* initial, uint32_t n_initial, const demi_dpor_params* params,
+                            const demi_wcdpor_params* wc, demi_dpor_trace_entry* out_trace /* [DEMI_DPOR_MAX_TRACE] */,
+                            demi_wcdpor_result* result);
+
 /* The whole bounded exploration in one call: the backtrack priority queue with
  * DefaultBacktrackOrdering (BacktrackOrdering.scala:58-69), the ExploredTacker
  * (AuxilaryTypes.scala:209-246), dpor()'s bookkeeping (:1068-1070, 1134) and getNext() (:1142-1185)

@@ -809,6 +809,62 @@ JNIEXPORT jint JNICALL FN(dporExplored)(JNIEnv* e, jclass c, jlong h, jlong inde
   return rc;
 }
 
+/* ---- demi_dpor_wildcard_batch: n interleavings whose next traces hold wildcards (DPORwHeuristics.scala:474-514), one launch.
+ *      prefixes byte[16 * stride * n], prefixLen int[n], params int[7]; outputs: verdicts long[2 * n], traces byte[16 * 256 * n],
+ *      traceLen int[n], ignored / wild long[4 * n], alts byte[16 * maxAlts * n] (demi_dpor_wild_alt), nAlts int[n] */
+JNIEXPORT jint JNICALL FN(dporWildcardBatch)(JNIEnv* e, jclass c, jlong h, jbyteArray prefixes, jintArray prefixLen, jint stride, jintArray params,
+                                             jboolean stopAfterNextTrace, jint maxAlts, jlongArray verdicts, jbyteArray traces, jintArray traceLen,
+                                             jlongArray ignored, jlongArray wild, jbyteArray alts, jintArray nAlts) {
+  (void)c;
+  demi_dpor_params par;
+  const int64_t n = LEN(prefixLen), esz = (int64_t)sizeof(demi_dpor_trace_entry);
+  if (dpor_params_of(e, params, &par) || n <= 0 || stride < 0 || stride > 256 || maxAlts < 0 || maxAlts > 256 ||
+      LEN(prefixes) < esz * stride * n || LEN(verdicts) < 2 * n || LEN(traces) < esz * DEMI_DPOR_MAX_TRACE * n || LEN(traceLen) < n ||
+      LEN(ignored) < 4 * n || LEN(wild) < 4 * n || (maxAlts && LEN(alts) < (int64_t)sizeof(demi_dpor_wild_alt) * maxAlts * n) || LEN(nAlts) < n)
+    return DEMI_ERR_INVALID_ARG;
+  void* pf = BYTES(prefixes); void* pl = INTS(prefixLen); void* v = LONGS(verdicts); void* tr = BYTES(traces); void* tl = INTS(traceLen);
+  void* ig = LONGS(ignored); void* wc = LONGS(wild); void* al = maxAlts ? BYTES(alts) : NULL; void* na = INTS(nAlts);
+  jint rc = (LOST(prefixes, pf) || LOST(prefixLen, pl) || LOST(verdicts, v) || LOST(traces, tr) || LOST(traceLen, tl) || LOST(ignored, ig) ||
+             LOST(wild, wc) || (maxAlts && LOST(alts, al)) || LOST(nAlts, na))
+                ? DEMI_ERR_INVALID_ARG
+                : demi_dpor_wildcard_batch(CTX(h), (const demi_dpor_trace_entry*)pf, (const uint32_t*)pl, (uint32_t)stride, (uint64_t)n, &par,
+                                           stopAfterNextTrace ? 1u : 0u, (uint32_t)maxAlts, (demi_verdict*)v, (demi_dpor_trace_entry*)tr,
+                                           (uint32_t*)tl, (uint64_t*)ig, (uint64_t*)wc, (demi_dpor_wild_alt*)al, (uint32_t*)na);
+  PUT_INTS(nAlts, na, 0); if (maxAlts) PUT_BYTES(alts, al, 0); PUT_LONGS(wild, wc, 0); PUT_LONGS(ignored, ig, 0); PUT_INTS(traceLen, tl, 0);
+  PUT_BYTES(traces, tr, 0); PUT_LONGS(verdicts, v, 0); PUT_INTS(prefixLen, pl, JNI_ABORT); PUT_BYTES(prefixes, pf, JNI_ABORT);
+  return rc;
+}
+
+/* ---- WildcardMinimizer.testWithDpor of one proposal (demi_wildcard_dpor_test, WildcardMinimizer.scala:67-114).  initial byte[16 * m]
+ *      (kind 3 / 4 entries); params int[7]; wc int[3] = dpor_budget, batch, max_alts; trace byte[16 * 256]; result long[16] =
+ *      hit, interleavings, speculated, launches, exhausted, budget_reached, retried, trace_len, skipped_explored, points, 0, 0,
+ *      ignored[0 .. 3] */
+JNIEXPORT jint JNICALL FN(wildcardDporTest)(JNIEnv* e, jclass c, jlong h, jbyteArray initial, jintArray params, jintArray wc, jbyteArray trace,
+                                            jlongArray result) {
+  (void)c;
+  demi_dpor_params par;
+  const int64_t n_init = LEN(initial), esz = (int64_t)sizeof(demi_dpor_trace_entry);
+  if (dpor_params_of(e, params, &par) || LEN(wc) != 3 || n_init < 0 || n_init % esz || !trace || LEN(trace) < esz * DEMI_DPOR_MAX_TRACE ||
+      LEN(result) != 16)
+    return DEMI_ERR_INVALID_ARG;
+  jint w[3];
+  (*e)->GetIntArrayRegion(e, wc, 0, 3, w);
+  demi_wcdpor_params wp = {(uint32_t)w[0], (uint32_t)w[1], (uint32_t)w[2], 0};
+  demi_wcdpor_result r;
+  memset(&r, 0, sizeof r);
+  void* it = BYTES(initial);
+  void* tr = BYTES(trace);
+  jint rc = (LOST(initial, it) || LOST(trace, tr)) ? DEMI_ERR_INVALID_ARG
+            : demi_wildcard_dpor_test(CTX(h), (const demi_dpor_trace_entry*)it, (uint32_t)(n_init / esz), &par, &wp, (demi_dpor_trace_entry*)tr, &r);
+  PUT_BYTES(trace, tr, 0);
+  PUT_BYTES(initial, it, JNI_ABORT);
+  jlong o[16] = {(jlong)r.hit, (jlong)r.interleavings, (jlong)r.speculated, (jlong)r.launches, (jlong)r.exhausted, (jlong)r.budget_reached,
+                 (jlong)r.retried, (jlong)r.trace_len, (jlong)r.skipped_explored, (jlong)r.points, 0, 0,
+                 (jlong)r.ignored[0], (jlong)r.ignored[1], (jlong)r.ignored[2], (jlong)r.ignored[3]};
+  SET_LONGS(result, 16, o);
+  return rc;
+}
+
 /* ---- ProvenanceTracker.pruneConcurrentEvents for a batch of traces: traces byte[16 * stride * n] (demi_dpor_trace_entry),
  *      traceLen int[n], affected int[n] (actor bitmasks), keep long[4 * n] */
 JNIEXPORT jint JNICALL FN(provenancePrune)(JNIEnv* e, jclass c, jlong h, jbyteArray traces, jintArray traceLen, jintArray affected,

@@ -158,6 +158,19 @@ object DemiGpu {
   /** What interleaving `index` of the last dporExplore was (demi_dpor_explored): nextTrace / trace = byte[16 * 256] (16-byte trace entries),
    *  lens = long[3] (next-trace length, its shared take() part, executed-trace length).  For diffing an exploration against DPORwHeuristics. */
   @native def dporExplored(h: Long, index: Long, nextTrace: Array[Byte], trace: Array[Byte], lens: Array[Long]): Int
+  /** n interleavings whose next traces hold wildcards, one launch (demi_dpor_wildcard_batch; DPORwHeuristics.scala:474-514): 16-byte
+   *  entries of kind 3 (a WildCardMatch: key = type set | policy << 32 | backtrack mode << 40) and 4 (Unique(_, -1) of an external
+   *  message, by word) beside kinds 0 / 1 / 2.  verdicts long[2 * n]; traces byte[16 * 256 * n]; ignored / wild long[4 * n]: 256 bits
+   *  each (ignoreAbsentCallback positions; trace entries a wildcard picked); alts byte[16 * maxAlts * n] (key, word, trace length,
+   *  position, producer index), nAlts int[n] */
+  @native def dporWildcardBatch(h: Long, prefixes: Array[Byte], prefixLen: Array[Int], stride: Int, params: Array[Int],
+                                stopAfterNextTrace: Boolean, maxAlts: Int, verdicts: Array[Long], traces: Array[Byte], traceLen: Array[Int],
+                                ignored: Array[Long], wild: Array[Long], alts: Array[Byte], nAlts: Array[Int]): Int
+  /** WildcardMinimizer.testWithDpor of one proposal in one call (demi_wildcard_dpor_test, WildcardMinimizer.scala:67-114): initial =
+   *  the proposal's uniques as 16-byte entries; params = int[7] (max_messages = uniques.size); wc = int[3] (dpor_budget - interleavings,
+   *  the reference's budgetSeconds as a count -, batch, max_alts); trace = byte[16 * 256]; result = long[16] (hit, interleavings,
+   *  speculated, launches, exhausted, budget_reached, retried, trace_len, skipped_explored, points, 0, 0, ignored[0 .. 3]) */
+  @native def wildcardDporTest(h: Long, initial: Array[Byte], params: Array[Int], wc: Array[Int], trace: Array[Byte], result: Array[Long]): Int
   /** RunnerUtils.editDistanceDporDDMin in one call (demi_edit_distance_dpor_ddmin: IncrementalDDMin over ResumableDPOR, every DPOR
    *  consultation inside the library).  externals = 8 bytes each; initialTrace = 16-byte entries (FlatEvents.dporInitialTrace);
    *  dporParams = int[7]; params = int[7] (max_max_distance, stop_at_size, check_unmodified, ignore_quiescence, verify_mcs, batch, budget);
