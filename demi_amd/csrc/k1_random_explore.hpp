@@ -543,6 +543,26 @@ __global__ K1_LAUNCH_BOUNDS void k1_random_explore(const typename K1ArgsOf<V>::t
 #endif
   };
   uint32_t viol = 0, flags = 0;
+  // One countdown for "something other than a plain delivery happens at this count": `until` = the deliveries left until the
+  // nearer of the next invariant checkpoint and count exceeding max_messages.  A delivery decrements it; the step tests it
+  // against zero and the branch taken there decides which of the two it is, in the reference's order, and reloads it.  That
+  // replaces, on the path of every delivery, count > max_messages, the checkpoint counter cnt_mod with its wrap and its three
+  // compares, and the step's own test of `viol` (which never fired: the quiescence branch ends a violating execution in the
+  // iteration of its checkpoint).
+  // A kernel compiled for one table has it; the table interpreter keeps the tests - it measured 0.8 % slower with the countdown
+  // (DESIGN 0.19).  (DEMI_K1_NO_EVENT_COUNTDOWN: those tests in the compiled kernel too, for A/B runs)
+#if defined(DEMI_JIT_A) && !defined(DEMI_K1_NO_EVENT_COUNTDOWN)
+  constexpr bool COUNTDOWN = true;
+#else
+  constexpr bool COUNTDOWN = false;
+#endif
+  // (both events seen from a fresh count of 0: the first checkpoint is `interval` deliveries away - count != 0, lastCheckpoint == 0,
+  // and interval == 0 means never; count > max_messages first holds max_messages + 1 deliveries away)
+  // (limit1: that distance, without the wrap of max_messages == 0xFFFFFFFF - a limit no 32-bit count exceeds, so its event is
+  // placed 2^32 - 1 deliveries away, further than any execution gets; the test of count against max_messages itself stays exact)
+  const uint32_t limit1 = (max_messages < 0xFFFFFFFEu ? max_messages : 0xFFFFFFFEu) + 1u;
+  const uint32_t until0 = (interval != 0 && interval < limit1) ? interval : limit1;
+  uint32_t until = until0;
   uint32_t blocked = 0;               // Instrumenter().blockedActors: actors that crashed (DEMI_OP_CRASH) and were not Start()ed since
   // a specialised build knows whether the table has a CRASH row at all (jit: DEMI_JIT_NO_CRASH): without one `blocked` is
   // provably 0 and the find_non_blocked_message path below is not even compiled
@@ -774,7 +794,7 @@ __global__ K1_LAUNCH_BOUNDS void k1_random_explore(const typename K1ArgsOf<V>::t
           sched++; exec_no++;
           ph = PH_INJECT; fresh = true;
         }
-        n_pend = 0; count = 0; cnt_mod = 0; tidx = 0; inj_lo = 0; inj_hi = 0; batch_no = 0;
+        n_pend = 0; count = 0; cnt_mod = 0; until = until0; tidx = 0; inj_lo = 0; inj_hi = 0; batch_no = 0;
         tq.clear(); resend.clear(); n_tq = 0; n_resend = 0; just = 0; rep = 0; inq = 0; viol = 0; flags = 0; hash = 0;
         n_norm = 0; n_pairs = 0; pairmask = 0;
       }
@@ -916,7 +936,21 @@ __global__ K1_LAUNCH_BOUNDS void k1_random_explore(const typename K1ArgsOf<V>::t
     bool deliver = false;
     const bool disp = (ph == PH_DISPATCH);
     bool none = false, step = false;
-    if (disp) {
+    if (disp && COUNTDOWN) {
+      // (a violation is only ever found at the checkpoint below, and that execution leaves there: `viol` is not tested, :354-360)
+      if (until == 0) {                                         // this count is a checkpoint, or the first one beyond max_messages
+        if (count > max_messages) {                             // :369-373 finish_early (no check, even where a checkpoint coincides)
+          flags |= DEMI_V_MAXMSG; tidx = E; none = true;
+        } else {                                                // :376-394 (lastCheckpoint == 0)
+          viol = check_invariant();
+          if (viol) none = true;                                // (the quiescence branch below ends the execution, as it always did)
+          const uint32_t room = limit1 - count;                 // (>= 1: count <= max_messages here, and below 2^32 - 1)
+          until = interval < room ? interval : room;            // (interval == 0 never gets here: its only event is the limit)
+        }
+      }
+      step = !none;
+    }
+    if (disp && !COUNTDOWN) {
       if (viol) {
         none = true;                                            // :354-360
       } else if (count > max_messages) {                        // :369-373 finish_early
@@ -1107,7 +1141,8 @@ __global__ K1_LAUNCH_BOUNDS void k1_random_explore(const typename K1ArgsOf<V>::t
           }
         }
         count++;
-        cnt_mod++; if (cnt_mod == interval) cnt_mod = 0;
+        if (COUNTDOWN) until--;
+        else { cnt_mod++; if (cnt_mod == interval) cnt_mod = 0; }
         const uint32_t type = w_type(w), me = w_dst(w);
         REC_PUSH(DEMI_REC_MSG_EVENT, w_src(w), me, type, w_area(w), 0, 255, wid);
         hash_step(hash, w);
