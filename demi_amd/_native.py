@@ -197,11 +197,28 @@ def specialize_check(model_struct):
     return int(n), log.value.decode()
 
 
-def specialize_source(model_struct, k1=False):
+def specialize_source(model_struct, k1=False, fx_commute=False):
     """The C++ the specialiser generates for the model's handlers (k1: the RandomScheduler kernel's flavour, with the
-    table's effect-slot schedule when it has one)."""
-    buf = C.create_string_buffer(1 << 20)
-    n = (lib().demi_specialize_source_k1 if k1 else lib().demi_specialize_source)(C.byref(model_struct), buf, len(buf))
+    table's effect-slot schedule when it has one).
+    fx_commute (k1 only): True = the schedule demi_model_specialize compiles by default, in which a timer-set row may sit below
+    a send that precedes it (jit.hpp fx_schedule); False = the schedule whose slot order is every path's program order - what
+    the library's switch DEMI_JIT_NO_FX_COMMUTE selects and what a table gets whose commuted schedule is not exact.  The C
+    entry point follows the switch; this wrapper sets it for the call, so that a caller reads one or the other by name."""
+    saved = {k: os.environ.get(k) for k in ("DEMI_EXPERIMENT", "DEMI_JIT_NO_FX_COMMUTE")}
+    try:
+        if k1 and not fx_commute:
+            os.environ["DEMI_EXPERIMENT"] = "1"
+            os.environ["DEMI_JIT_NO_FX_COMMUTE"] = "1"
+        elif k1:
+            os.environ.pop("DEMI_JIT_NO_FX_COMMUTE", None)
+        buf = C.create_string_buffer(1 << 20)
+        n = (lib().demi_specialize_source_k1 if k1 else lib().demi_specialize_source)(C.byref(model_struct), buf, len(buf))
+    finally:
+        for k, v in saved.items():
+            if v is None:
+                os.environ.pop(k, None)
+            else:
+                os.environ[k] = v
     if n < 0:
         raise DemiError(n, buf.value.decode(errors="replace"))
     return buf.value.decode()

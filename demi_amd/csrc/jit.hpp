@@ -38,10 +38,22 @@ namespace demi_jit {
 // then one pass over the row DAG that fixes every row's slot and extends the schedule where the paths of one row disagree).
 // Not applicable (the dynamic queue is kept) when some path holds more than DEMI_FX_CAP effect rows - the queue overflow
 // is then a possible verdict - or the schedule needs more than DEMI_FX_CAP slots.
+//
+// Commuting classes (`commute`): a TSET / TREP row and a SEND / BCAST row touch disjoint state (timer queues and registered
+// timers against the pending set), so a timer-set row may take a slot BELOW the slot of a send that precedes it on its path:
+// the row is then "moved", and a handler that sets its timer after its send shares the slot of the handlers that set it
+// before.  Nothing else commutes (a cancel edits both the pending set and the timer queue), and a timer-set row never goes
+// above a send that follows it.  The two kinds meet in one place, the capacity verdict: a moved row runs before sends that
+// the program runs first, so its queue overflow must not keep those sends from being evaluated (K1's apply phase,
+// DEMI_JIT_FX_MOVED_SLOTS).  That is exact only when every send in a later slot than a moved row precedes the row on every
+// path through it; every path is checked, and a table that fails the check (or has too many paths to check) gets the
+// schedule without commutation.
 struct FxSchedule {
   bool ok = false;
   std::vector<uint32_t> cls;        // per slot: kind << 16 | op << 8 | type   (kind 0: send, op / type unused)
   std::vector<int32_t> slot;        // per row: its slot, -1 for rows that are not effect rows
+  std::vector<uint8_t> moved;       // per row: a timer-set row whose slot lies below the slot of a send that precedes it on some path
+  bool any_moved() const { return std::find(moved.begin(), moved.end(), (uint8_t)1) != moved.end(); }
 };
 enum : uint32_t { FXK_SEND = 0, FXK_CANCEL = 1, FXK_TSET = 2, FXK_CRASH = 3 };
 inline uint32_t fx_class_of(uint32_t row) {
@@ -51,11 +63,21 @@ inline uint32_t fx_class_of(uint32_t row) {
   if (op == DEMI_OP_TSET || op == DEMI_OP_TREP) return (FXK_TSET << 16) | (op << 8) | type;
   return FXK_CRASH << 16;
 }
-inline FxSchedule fx_schedule(const demi::DevModel& h) {
+// two effect classes whose rows may be applied in either order
+inline bool fx_commute(uint32_t a, uint32_t b) {
+  const uint32_t ka = a >> 16, kb = b >> 16;
+  return (ka == FXK_TSET && kb == FXK_SEND) || (ka == FXK_SEND && kb == FXK_TSET);
+}
+// pinned: timer-set rows that keep their place behind the sends that precede them (the search below pins rows itself)
+inline FxSchedule fx_schedule_search(const demi::DevModel& h, bool commute, std::vector<uint8_t> pinned = {}) {
   using namespace demi;
   FxSchedule S;
   const uint32_t n = h.code_len;
   S.slot.assign(n, -1);
+  S.moved.assign(n, 0);
+  pinned.resize(n, 0);
+  // a timer-set row that may change places with the sends around it
+  auto free_tset = [&](uint32_t pc) { return commute && !pinned[pc] && (fx_class_of(h.code[pc]) >> 16) == FXK_TSET; };
   // successors of a row (n = the handler is done)
   auto succ = [&](uint32_t pc, uint32_t out[2]) -> int {
     const uint32_t row = h.code[pc], cw = op_control(row & 0x3Fu);
@@ -83,10 +105,9 @@ inline FxSchedule fx_schedule(const demi::DevModel& h) {
     most[pc] = m + (is_fx(pc) ? 1u : 0u);
   }
   for (uint32_t st : starts) if (most[st] > DEMI_FX_CAP) return S;
-  // the distinct effect-class sequences of the handlers' paths (bounded enumeration; beyond the bound the DAG pass below
-  // still produces a valid schedule, only a longer one)
-  std::vector<std::vector<uint32_t>> seqs;
-  {
+  // every path of every handler as the list of its effect rows: fn(rows) per path, false when the bound on the number of
+  // paths ran out before the last one
+  auto each_path = [&](auto&& fn) -> bool {
     size_t budget = 20000;
     std::vector<uint32_t> cur;
     struct Frame { uint32_t pc; int next; size_t depth; };
@@ -97,7 +118,7 @@ inline FxSchedule fx_schedule(const demi::DevModel& h) {
       while (!stack.empty() && budget) {
         Frame& f = stack.back();
         if (f.pc >= n) {
-          if (!cur.empty() && std::find(seqs.begin(), seqs.end(), cur) == seqs.end()) seqs.push_back(cur);
+          fn(cur);
           budget--;
           stack.pop_back();
           continue;
@@ -106,9 +127,9 @@ inline FxSchedule fx_schedule(const demi::DevModel& h) {
         const int k = succ(f.pc, o);
         if (f.next == 0) {
           f.depth = cur.size();
-          if (is_fx(f.pc)) cur.push_back(fx_class_of(h.code[f.pc]));
+          if (is_fx(f.pc)) cur.push_back(f.pc);
           if (k == 0) {
-            if (!cur.empty() && std::find(seqs.begin(), seqs.end(), cur) == seqs.end()) seqs.push_back(cur);
+            fn(cur);
             budget--;
           }
         }
@@ -122,8 +143,28 @@ inline FxSchedule fx_schedule(const demi::DevModel& h) {
           stack.pop_back();
         }
       }
+      if (!stack.empty()) return false;
     }
-  }
+    return true;
+  };
+  // the distinct effect-class sequences of the handlers' paths (bounded enumeration; beyond the bound the DAG pass below
+  // still produces a valid schedule, only a longer one).  With commuting classes every sequence is first brought into its
+  // normal form: within a run of (free) timer-set rows and send rows the timer sets come first, each kind in its own order.
+  std::vector<std::vector<uint32_t>> seqs;
+  const bool all_paths = each_path([&](const std::vector<uint32_t>& path) {
+    if (path.empty()) return;
+    std::vector<uint32_t> rows = path, q;
+    if (commute)
+      for (size_t i = 0; i < rows.size();) {
+        size_t e = i;
+        while (e < rows.size() && (free_tset(rows[e]) || (fx_class_of(h.code[rows[e]]) >> 16) == FXK_SEND)) e++;
+        std::stable_partition(rows.begin() + i, rows.begin() + e, [&](uint32_t pc) { return free_tset(pc); });
+        i = e + 1;
+      }
+    for (uint32_t pc : rows) q.push_back(fx_class_of(h.code[pc]));
+    if (std::find(seqs.begin(), seqs.end(), q) == seqs.end()) seqs.push_back(q);
+  });
+  if (commute && !all_paths) return fx_schedule_search(h, false);     // (the check below needs every path)
   // a cheap common supersequence of those sequences.  First guess: majority merge (the class at the front of the most
   // remaining sequences comes next); then a bounded branch-and-bound over "which front class next" looks for a cheaper one
   // (cost = the bodies the kernel will execute per delivery: a send or a cancel body is about twice a timer-set body)
@@ -185,23 +226,56 @@ inline FxSchedule fx_schedule(const demi::DevModel& h) {
     } rec{seqs, S.cls, best_cost, nodes, weight};
     rec.go(pos, cur, 0);
   }
-  // fix every row's slot: the first slot of its class after the slots of every effect row that can precede it
-  std::vector<int32_t> lo(n + 1, -1);                            // -1: not reachable
+  // fix every row's slot: the first slot of its class after the slots of every effect row that can precede it - for a
+  // free timer-set row, of every preceding row that is no send (lo_t)
+  std::vector<int32_t> lo(n + 1, -1), lo_t(n + 1, 0);            // lo -1: not reachable
   for (uint32_t st : starts) lo[st] = 0;
   for (uint32_t pc = 0; pc < n; pc++) {
     if (lo[pc] < 0) continue;
-    int32_t next = lo[pc];
+    int32_t next = lo[pc], next_t = lo_t[pc];
     if (is_fx(pc)) {
-      const uint32_t c = fx_class_of(h.code[pc]);
-      int32_t j = next;
+      const uint32_t c = fx_class_of(h.code[pc]), kind = c >> 16;
+      int32_t j = free_tset(pc) ? next_t : next;
       while (j < (int32_t)S.cls.size() && S.cls[j] != c) j++;
       if (j >= (int32_t)S.cls.size()) { S.cls.push_back(c); j = (int32_t)S.cls.size() - 1; }
       S.slot[pc] = j;
-      next = j + 1;
+      next = std::max(next, j + 1);
+      if (kind != FXK_SEND) next_t = std::max(next_t, j + 1);
     }
     uint32_t o[2];
     const int k = succ(pc, o);
-    for (int i = 0; i < k; i++) if (o[i] < n) lo[o[i]] = std::max(lo[o[i]], next);
+    for (int i = 0; i < k; i++) if (o[i] < n) { lo[o[i]] = std::max(lo[o[i]], next); lo_t[o[i]] = std::max(lo_t[o[i]], next_t); }
+  }
+  if (commute) {
+    // which rows were moved - a send that precedes the row on some path sits in a later slot - and the check of every path.
+    // Rows that do not commute keep their order and no timer-set row went above a send that follows it: by construction.
+    // A delivery that ran a moved row says so in ONE bit (DEMI_FX_MARK_MOVED), and K1's apply phase then lets a queue overflow
+    // pass the send slots: exact when, on every path that holds a moved row, every send in a later slot than ANY timer-set row
+    // of the path precedes that row in the program.  Where a path fails that, its moved rows are pinned and the search runs again.
+    bool good = true, pins = false;
+    each_path([&](const std::vector<uint32_t>& rows) {
+      for (size_t j = 0; j < rows.size(); j++)
+        for (size_t i = 0; i < j; i++) {
+          const uint32_t ci = fx_class_of(h.code[rows[i]]), cj = fx_class_of(h.code[rows[j]]);
+          const int32_t si = S.slot[rows[i]], sj = S.slot[rows[j]];
+          if (si < sj) continue;
+          if (fx_commute(ci, cj) && free_tset(rows[j]) && si != sj) S.moved[rows[j]] = 1;
+          else good = false;
+        }
+    });
+    each_path([&](const std::vector<uint32_t>& rows) {
+      bool has_moved = false, exact = true;
+      for (uint32_t pc : rows) has_moved |= S.moved[pc] != 0;
+      if (!has_moved) return;
+      for (size_t j = 0; j < rows.size(); j++) {
+        if ((fx_class_of(h.code[rows[j]]) >> 16) != FXK_TSET) continue;
+        for (size_t i = j + 1; i < rows.size(); i++)
+          if ((fx_class_of(h.code[rows[i]]) >> 16) == FXK_SEND && S.slot[rows[i]] > S.slot[rows[j]]) exact = false;
+      }
+      if (!exact) for (uint32_t pc : rows) if (S.moved[pc]) { pinned[pc] = 1; pins = true; }
+    });
+    if (!good) return fx_schedule_search(h, false);
+    if (pins) return fx_schedule_search(h, true, pinned);
   }
   // slots nobody uses (the merge saw a path the DAG pass placed elsewhere) are dropped
   {
@@ -216,10 +290,21 @@ inline FxSchedule fx_schedule(const demi::DevModel& h) {
   return S;
 }
 
+// The schedule of a table: the one with commuting classes, unless it moves no row or pinning rows made it dearer (same weights as
+// the search) than the schedule whose slot order is every path's program order - which is also what commute off gives.
+inline FxSchedule fx_schedule(const demi::DevModel& h, bool commute = true) {
+  const FxSchedule plain = fx_schedule_search(h, false);
+  if (!commute) return plain;
+  const FxSchedule moved = fx_schedule_search(h, true);
+  if (!moved.ok || !moved.any_moved()) return plain;
+  auto cost = [](const FxSchedule& s) { uint32_t c = 0; for (uint32_t x : s.cls) c += (x >> 16) == FXK_TSET ? 2u : ((x >> 16) == FXK_CRASH ? 1u : 4u); return c; };
+  return (!plain.ok || cost(moved) <= cost(plain)) ? moved : plain;
+}
+
 // effect-queue entries the scheduled K1 of a table needs (its SEND / BCAST slots), DEMI_FX_CAP without a schedule
-inline uint32_t k1_fxq_slots(const demi::DevModel& h, bool sched) {
+inline uint32_t k1_fxq_slots(const demi::DevModel& h, bool sched, bool commute = true) {
   if (!sched) return DEMI_FX_CAP;
-  const FxSchedule fxs = fx_schedule(h);
+  const FxSchedule fxs = fx_schedule(h, commute);
   if (!fxs.ok) return DEMI_FX_CAP;
   uint32_t nq = 0;
   for (uint32_t c : fxs.cls) nq += (c >> 16) == FXK_SEND;
@@ -266,14 +351,15 @@ inline std::string init_hits_define(const demi::DevModel& h) {
 // guarantees it), handler entry is a switch over the distinct handler starts.
 // `sched`: K1's flavour with the static effect-slot schedule above (vm_run_jit then returns the mask of filled slots);
 // without it, or when no schedule exists, effect rows are queued in program order as vm_run does (K2 / K3).
-inline std::string generate_vm(const demi::DevModel& h, bool sched = false) {
+// `commute`: the schedule may move timer-set rows below the sends that precede them (fx_schedule).
+inline std::string generate_vm(const demi::DevModel& h, bool sched = false, bool commute = true) {
   using namespace demi;
   std::string s;
   char buf[512];
   auto emit = [&](const char* fmt, auto... a) { snprintf(buf, sizeof buf, fmt, a...); s += buf; };
   FxSchedule fxs;
   std::vector<uint32_t> fxq_of_slot;
-  if (sched) fxs = fx_schedule(h);
+  if (sched) fxs = fx_schedule(h, commute);
   if (fxs.ok) {
     // the schedule for the kernel's apply phase: one DEMI_FX_SLOT(slot, kind, op, type, timer index) per slot, in order
     // (only the SEND / BCAST slots carry data: they get the entries 0, 1, ... of the effect queue, DEMI_JIT_FXQ_SLOTS in all)
@@ -287,6 +373,12 @@ inline std::string generate_vm(const demi::DevModel& h, bool sched = false) {
       if (snd) nq++;
     }
     emit("\n#define DEMI_JIT_FXQ_SLOTS %uu\n", nq ? nq : 1u);
+    if (fxs.any_moved()) {
+      // the slots that hold a moved row: their queue overflow may have to wait for sends the program runs first (K1's apply phase)
+      uint32_t mv = 0;
+      for (uint32_t pc = 0; pc < h.code_len; pc++) if (fxs.moved[pc]) mv |= 1u << fxs.slot[pc];
+      emit("#define DEMI_JIT_FX_MOVED_SLOTS 0x%xu\n", mv);
+    }
   }
   s += "namespace demi {\n";
   // (PAY: the two payload operands of the row - or, for a table with DEMI_MODEL_PAYLOADS, the payload area with the staged
@@ -296,7 +388,10 @@ inline std::string generate_vm(const demi::DevModel& h, bool sched = false) {
   if (fxs.ok)
     // an effect row fills its own slot of the schedule; only SEND / BCAST rows carry data (a timer row IS its slot)
     s += std::string("#define DEMI_FX_AT(SLOT, Q, OP, TYPE, TGT, ...) { mem.fxq[(Q) * 64] = ") + fx_pack_fn + "(OP, TYPE, TGT, __VA_ARGS__); nfx |= 1u << (SLOT); }\n"
-         "#define DEMI_FX_MARK(SLOT) { nfx |= 1u << (SLOT); }\n";
+         "#define DEMI_FX_MARK(SLOT) { nfx |= 1u << (SLOT); }\n"
+         // (a moved row says so above the slots' bits - nfx >> DEMI_FX_CAP is then the flag the send slots let pass: the slot's
+         // body is shared with rows that were not moved)
+         "#define DEMI_FX_MARK_MOVED(SLOT) { nfx |= (1u << (SLOT)) | (DEMI_V_QUEUE_OVF << DEMI_FX_CAP); }\n";
   else
     // effect rows are recorded into the LDS effect queue in program order, exactly as vm_run does
     s += std::string("#define DEMI_FX(OP, TYPE, TGT, ...) { if (nfx >= DEMI_FX_CAP) { flags |= DEMI_V_QUEUE_OVF; goto done; } "
@@ -443,7 +538,7 @@ inline std::string generate_vm(const demi::DevModel& h, bool sched = false) {
       if (long_msg) snprintf(pay, sizeof pay, "pay_area(%s, %s, q2, q3, q4, q5)", d, b);
       else snprintf(pay, sizeof pay, "%s, %s", d, b);
       if (fxs.ok && (fxs.cls[fxs.slot[pc]] >> 16) != FXK_SEND)
-        emit("DEMI_FX_MARK(%d)%s\n", fxs.slot[pc], (cw & CW_HALT) ? " goto done;" : "");
+        emit("DEMI_FX_MARK%s(%d)%s\n", fxs.moved[pc] ? "_MOVED" : "", fxs.slot[pc], (cw & CW_HALT) ? " goto done;" : "");
       else if (fxs.ok)
         emit("DEMI_FX_AT(%d, %uu, %uu, %uu, %s > FX_NOBODY ? FX_NOBODY : %s, %s)\n", fxs.slot[pc], fxq_of_slot[fxs.slot[pc]], row & 0xFFu, aux, a, a, pay);
       else      // (a target beyond the field - sim_core.hpp FX_NOBODY: 15, 31 in the BIG layout - is nobody)

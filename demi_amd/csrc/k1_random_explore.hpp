@@ -607,10 +607,17 @@ __global__ K1_LAUNCH_BOUNDS void k1_random_explore(const typename K1ArgsOf<V>::t
     }                                                                                         \
   } while (0)
 
+// K1_PENDING_OVF: what an append does that finds the pending set full.  In a kernel whose effect schedule moved timer-set rows
+// below sends (DEMI_JIT_FX_MOVED_SLOTS, see the apply phase) the queue flag can be set at that point - by a moved row, which
+// the program runs after the send: the verdict is then the pending flag alone.  One instruction either way.
+#ifndef DEMI_JIT_FX_MOVED_SLOTS
+#define DEMI_JIT_FX_MOVED_SLOTS 0u
+#endif
+#define K1_PENDING_OVF() (flags = DEMI_JIT_FX_MOVED_SLOTS ? ((flags & ~DEMI_V_QUEUE_OVF) | DEMI_V_PENDING_OVF) : (flags | DEMI_V_PENDING_OVF))
 // TD_ENTRY: the timer directory entry of a timer message (>= 0: it now has a copy in slot n_pend), -1 for anything else
 #define PEND_APPEND(WORD, ID, TD_ENTRY)                               \
   do {                                                                \
-    if (n_pend + n_norm >= PMAX) { flags |= DEMI_V_PENDING_OVF; }     \
+    if (n_pend + n_norm >= PMAX) { K1_PENDING_OVF(); }                \
     else {                                                            \
       pend_store(mem, n_pend, (WORD));                                \
       LASTW_SET(WORD);                                                \
@@ -627,7 +634,7 @@ __global__ K1_LAUNCH_BOUNDS void k1_random_explore(const typename K1ArgsOf<V>::t
 // srcDsts entry) when the pair has none
 #define NORM_APPEND(WORD, ID)                                         \
   do {                                                                \
-    if (n_pend + n_norm >= PMAX) { flags |= DEMI_V_PENDING_OVF; }     \
+    if (n_pend + n_norm >= PMAX) { K1_PENDING_OVF(); }                \
     else {                                                            \
       const word_t w_ = (WORD);                                       \
       const uint32_t pr_ = w_src(w_) * MAX_ACT + w_dst(w_);           \
@@ -1357,8 +1364,21 @@ __global__ K1_LAUNCH_BOUNDS void k1_random_explore(const typename K1ArgsOf<V>::t
       // A table compiled with an effect schedule (jit.hpp fx_schedule): every effect row has a fixed slot whose class -
       // send, or (timer op, timer type) - is a compile-time constant, slots increase along every path of every handler
       // (program order), and `nfx` is the mask of the slots this delivery filled: one straight pass, each body once.
+      // A schedule with commuting classes may have MOVED a timer-set row below the slot of a send that precedes it in the
+      // program (DEMI_JIT_FX_MOVED_SLOTS: the slots with such a row).  The two bodies touch disjoint state, so only the capacity
+      // verdict sees the order: the moved row's queue overflow must not keep the sends the program runs first from being
+      // evaluated, and the verdict is the pending flag alone when one of them overflows.  A delivery that ran a moved row
+      // says so in nfx (DEMI_FX_MARK_MOVED: nfx >> DEMI_FX_CAP is DEMI_V_QUEUE_OVF, else 0): its send slots stop at the pending
+      // flag only - fx_schedule checked on every path of such a delivery that the sends in later slots than a timer-set row
+      // all precede that row - and a send that overflows takes the queue flag back (PEND_APPEND, NORM_APPEND).  Timer, cancel and
+      // crash slots stop at either flag, as they always did: they follow the row that overflowed.
+#ifdef DEMI_K1_FX_DROP_MOVED      // (broken on purpose, for the test that shows the overflow matrix notices: no delivery counts as moved)
+      const uint32_t fx_send_stop = DEMI_OVF_ANY;
+#else
+      const uint32_t fx_send_stop = DEMI_JIT_FX_MOVED_SLOTS ? (DEMI_OVF_ANY ^ (nfx >> DEMI_FX_CAP)) : DEMI_OVF_ANY;
+#endif
 #define DEMI_FX_SLOT(J, KIND, OP, TYPE, TIDX, Q)                                                                      \
-      if (((nfx >> (J)) & 1u) && !(flags & DEMI_OVF_ANY)) {                                                           \
+      if (((nfx >> (J)) & 1u) && !(flags & ((KIND) == 0u ? fx_send_stop : DEMI_OVF_ANY))) {                            \
         if ((KIND) == 0u) apply_send(mem.fxq[(Q) * 64]);                     /* (Q: the slot's entry of the effect queue) */ \
         else if ((KIND) == 1u) apply_cancel((TYPE), (tmask_t)1 << (me * DEMI_MAX_TIMER_TYPES + (TIDX)), (TIDX));               \
         else if ((KIND) == 2u) apply_timer_set((OP) == DEMI_OP_TREP, (TYPE), (tmask_t)1 << (me * DEMI_MAX_TIMER_TYPES + (TIDX))); \
@@ -1432,6 +1452,7 @@ __global__ K1_LAUNCH_BOUNDS void k1_random_explore(const typename K1ArgsOf<V>::t
 #undef PH_MARK
 #undef REC_PUSH
 #undef PEND_APPEND
+#undef K1_PENDING_OVF
 #undef NORM_APPEND
 #undef LASTW
 #undef LASTW_SET
