@@ -1040,7 +1040,8 @@ class Context:
 
     def device_probe(self, waves_per_simd=1, iters=20000, kind=0):
         """Shader clock under load (GHz) and SIMD cycles per wave64 instruction of the probe's kind: 0 integer VALU,
-        1 SALU, 2 VALU / SALU alternating, 3 a divergent `if` (demi_device_probe_mix)."""
+        1 SALU, 2 VALU / SALU alternating, 3 a divergent `if`, 4 - 7 one opcode alone: v_add_u32, v_mul_lo_u32, v_mul_hi_u32,
+        v_mad_u64_u32 (demi_device_probe_mix)."""
         r = T.ProbeResult()
         self._check(lib().demi_device_probe_mix(self._h, waves_per_simd, iters, kind, C.byref(r)))
         return r

@@ -23,6 +23,30 @@
 #define DEMI_VM_RUN vm_run
 #endif
 
+// K1_RARE(c): `c` holds for a lane about never, and with 56 lanes delivering still for none of the wave in most iterations
+// (tools/k1_empty_census.py has the table).  The wave pays for every instruction of a short divergent branch
+// whether or not a lane takes it - the compiler guards only long bodies with s_cbranch_execz - so the hint moves such a body
+// out of the delivery loop's straight line, behind a branch the wave does not follow when no lane wants it.  A kernel
+// compiled for one table has the hints; the table interpreter keeps its block order.  (DEMI_K1_NO_RARE: plain conditions in
+// the compiled kernel too, for A/B runs.)  Plain C++: the emulator's g++ builds read it as well.
+#if defined(DEMI_JIT_A) && !defined(DEMI_K1_NO_RARE)
+#define K1_RARE(c) __builtin_expect(!!(c), 0)
+#define K1_HINTS 1
+#else
+#define K1_RARE(c) (c)
+#define K1_HINTS 0
+#endif
+// K1_SITE(n): the census build (DEMI_K1_CENSUS, emulator only: it prints) notes that this lane entered source site n in the
+// running iteration; the end of the iteration counts, per site, the iterations in which no lane of the wave did.
+#ifdef DEMI_K1_CENSUS
+#define K1_SITE(n) (cz_bits |= 1u << (n))
+#define K1_CZ (&cz_bits)
+#define K1_SITES 12
+#else
+#define K1_SITE(n) ((void)0)
+#define K1_CZ nullptr
+#endif
+
 namespace demi {
 
 struct K1Args {
@@ -86,6 +110,31 @@ template <> struct K1ArgsOf<K1_SPREAD> { typedef K1SpreadArgs type; };
 template <> struct K1ArgsOf<K1_TESTS> { typedef K1TestsArgs type; };
 
 enum : int { PH_IDLE = 0, PH_INJECT = 1, PH_DISPATCH = 2, PH_FINISH = 3 };
+
+// jr_next_int (demi_device.hpp) for the pick of K1: the same draws, with the rejected draw - a lane meets one with probability
+// about bound / 2^31 - as a loop of its own behind the first draw's test, so that the hint can keep its two multiplies and
+// the loop's mask bookkeeping out of every iteration.  Without the hints it IS jr_next_int.  (cz: the census build's site bits)
+__device__ __forceinline__ uint32_t k1_next_int(uint64_t& s, uint32_t bound, const uint32_t* magic, uint32_t* cz = nullptr) {
+#if K1_HINTS
+  uint32_t r = jr_next31(s);
+  if ((bound & (bound - 1)) == 0) return r >> (__builtin_clz(bound));
+  if (cz) *cz |= 1u << 3;
+  const uint32_t m = magic[bound];
+  const uint32_t sh = 31 - __builtin_clz(bound - 1);
+  uint32_t qd = (__umulhi(r, m) >> sh) * bound;
+  if (K1_RARE((qd + bound - 1) >= 0x80000000u)) {
+    if (cz) *cz |= 1u << 4;
+    do {
+      r = jr_next31(s);
+      qd = (__umulhi(r, m) >> sh) * bound;
+    } while ((qd + bound - 1) >= 0x80000000u);
+  }
+  return r - qd;
+#else
+  (void)cz;
+  return jr_next_int(s, bound, magic);
+#endif
+}
 
 constexpr int K1_WAVES = 4;          // waves per workgroup
 // LDS-resident pending slots per lane in K1.  The interpreter is VALU-bound and wants residency (32: 12 waves/CU).  The
@@ -511,6 +560,9 @@ __global__ K1_LAUNCH_BOUNDS void k1_random_explore(const typename K1ArgsOf<V>::t
   uint64_t reach = 0;                 // !REC: the batch's reach matrix (K1_BATCH_WORDS above; BIG: read from the batch table instead)
   TimerQ tq = {0}, resend = {0};      // messagesToSend timers / timersToResend (demi_device.hpp TimerQ)
   uint32_t n_tq = 0, n_resend = 0;
+#ifdef DEMI_K1_CENSUS
+  uint32_t cz_bits = 0, cz_iters = 0, cz_empty[K1_SITES] = {0}, cz_lanes[K1_SITES] = {0};
+#endif
   tmask_t just = 0, rep = 0;          // justScheduledTimers / registered repeating timers (bit rcv*4+tidx)
   // The timers that MAY have an entry in tq (same bits): set by every enqueue into tq, cleared when the flush empties it, never
   // cleared by a removal - a superset.  A cancel searches tq only for a timer in it: tq is non-empty during most apply phases
@@ -617,7 +669,7 @@ __global__ K1_LAUNCH_BOUNDS void k1_random_explore(const typename K1ArgsOf<V>::t
 // TD_ENTRY: the timer directory entry of a timer message (>= 0: it now has a copy in slot n_pend), -1 for anything else
 #define PEND_APPEND(WORD, ID, TD_ENTRY)                               \
   do {                                                                \
-    if (n_pend + n_norm >= PMAX) { K1_PENDING_OVF(); }                \
+    if (K1_RARE(n_pend + n_norm >= PMAX)) { K1_SITE(8); K1_PENDING_OVF(); } \
     else {                                                            \
       pend_store(mem, n_pend, (WORD));                                \
       LASTW_SET(WORD);                                                \
@@ -634,7 +686,7 @@ __global__ K1_LAUNCH_BOUNDS void k1_random_explore(const typename K1ArgsOf<V>::t
 // srcDsts entry) when the pair has none
 #define NORM_APPEND(WORD, ID)                                         \
   do {                                                                \
-    if (n_pend + n_norm >= PMAX) { K1_PENDING_OVF(); }                \
+    if (K1_RARE(n_pend + n_norm >= PMAX)) { K1_SITE(8); K1_PENDING_OVF(); } \
     else {                                                            \
       const word_t w_ = (WORD);                                       \
       const uint32_t pr_ = w_src(w_) * MAX_ACT + w_dst(w_);           \
@@ -651,11 +703,11 @@ __global__ K1_LAUNCH_BOUNDS void k1_random_explore(const typename K1ArgsOf<V>::t
   auto enqueue_timer = [&](uint32_t rcv, uint32_t type, tmask_t tbit) {      // tbit = TIMER_BIT(rcv, type)
     const uint32_t b = TimerQ::pack(rcv, type, (BIG_TU || TQ_NARROW) ? tix_of(type) : 0u);
     if (just & tbit) {
-      if (n_resend >= DEMI_RESEND_CAP) { flags |= DEMI_V_QUEUE_OVF; return; }
+      if (K1_RARE(n_resend >= DEMI_RESEND_CAP)) { K1_SITE(7); flags |= DEMI_V_QUEUE_OVF; return; }
       resend.push(n_resend, b);
       n_resend++;
     } else {
-      if (n_tq >= DEMI_TQ_CAP) { flags |= DEMI_V_QUEUE_OVF; return; }
+      if (K1_RARE(n_tq >= DEMI_TQ_CAP)) { K1_SITE(7); flags |= DEMI_V_QUEUE_OVF; return; }
       tq.push(n_tq, b);
       n_tq++;
       if (INQ) inq |= tbit;
@@ -945,7 +997,7 @@ __global__ K1_LAUNCH_BOUNDS void k1_random_explore(const typename K1ArgsOf<V>::t
     bool none = false, step = false;
     if (disp && COUNTDOWN) {
       // (a violation is only ever found at the checkpoint below, and that execution leaves there: `viol` is not tested, :354-360)
-      if (until == 0) {                                         // this count is a checkpoint, or the first one beyond max_messages
+      if (until == 0) {                                         K1_SITE(0); // this count is a checkpoint, or the first one beyond max_messages
         if (count > max_messages) {                             // :369-373 finish_early (no check, even where a checkpoint coincides)
           flags |= DEMI_V_MAXMSG; tidx = E; none = true;
         } else {                                                // :376-394 (lastCheckpoint == 0)
@@ -1004,7 +1056,8 @@ __global__ K1_LAUNCH_BOUNDS void k1_random_explore(const typename K1ArgsOf<V>::t
       if (__ballot(spilled) != 0) __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
 #endif
       if (step && fl_cnt != 0) {
-        if (n_pend + n_norm + fl_cnt > PMAX) { flags |= DEMI_V_PENDING_OVF; n_pend = PMAX - n_norm; }
+        K1_SITE(1);
+        if (K1_RARE(n_pend + n_norm + fl_cnt > PMAX)) { K1_SITE(8); flags |= DEMI_V_PENDING_OVF; n_pend = PMAX - n_norm; }
         else { n_pend += fl_cnt; LASTW_SET(s_bsend[fl_off + fl_cnt - 1]); }     // (an overflowing execution ends here)
         fl_cnt = 0;
       }
@@ -1031,6 +1084,7 @@ __global__ K1_LAUNCH_BOUNDS void k1_random_explore(const typename K1ArgsOf<V>::t
         if (!drop) PEND_APPEND(msg_word(type, DL, rcv, 0, 0), id, (int32_t)(TQ_NARROW ? bt : rcv * NTT + tix_of(type)));
         REC_PUSH(DEMI_REC_MSG_SEND, DL, rcv, type, 0, 2 | (drop ? 4 : 0), 255, id);
       }
+      if (n_tq != 0) K1_SITE(2);
       tq.clear(); n_tq = 0; inq = 0;
       if ((flags & DEMI_OVF_ANY) || n_pend + n_norm == 0) none = true;
     }
@@ -1130,21 +1184,21 @@ __global__ K1_LAUNCH_BOUNDS void k1_random_explore(const typename K1ArgsOf<V>::t
           uint32_t idx = 0;
           if (!FIFO) {
             // FullyRandom.removeRandomElement -> RandomizedHashSet: nextInt(arr.length), swap with last
-            idx = jr_next_int(rng, n_pend, t.magic);
+            idx = k1_next_int(rng, n_pend, t.magic, K1_CZ);
           } else if (n_pairs == 0) {
             // SrcDstFIFO.getNonBlockedMessage (:716-729): only timers / externals left
-            idx = jr_next_int(te_rng, n_pend, t.magic);
+            idx = k1_next_int(te_rng, n_pend, t.magic, K1_CZ);
           } else {
             // (:731-759) a timer / external with probability |timersAndExternals| / |allMessages|, else a random pair's head
-            from_te = jr_next_int(rng, n_pend + n_norm, t.magic) < n_pend;
-            if (from_te) idx = jr_next_int(te_rng, n_pend, t.magic);
+            from_te = k1_next_int(rng, n_pend + n_norm, t.magic, K1_CZ) < n_pend;
+            if (from_te) idx = k1_next_int(te_rng, n_pend, t.magic, K1_CZ);
           }
           if (from_te) {
             w = pend_load(mem, idx);
             if (REC) wid = aux_load(mem, idx);
             pend_remove(idx, w, LASTW());
           } else {
-            fifo_dequeue(jr_next_int(rng, n_pairs, t.magic));
+            fifo_dequeue(k1_next_int(rng, n_pairs, t.magic, K1_CZ));
           }
         }
         count++;
@@ -1157,12 +1211,14 @@ __global__ K1_LAUNCH_BOUNDS void k1_random_explore(const typename K1ArgsOf<V>::t
         const tmask_t tbit = TIMER_BIT(me, type);
         const bool is_rep = ((timer_types >> type) & 1u) && (rep & tbit);
         if (is_rep) {
+          K1_SITE(5);
           just |= tbit;
           enqueue_timer(me, type, tbit);      // parked in timersToResend (it is in justScheduledTimers)
         } else {
           // timersToResend re-enter messagesToSend in order (RandomScheduler.scala:416-419): one shifted OR
           if (n_resend != 0) {
-            if (n_tq + n_resend > DEMI_TQ_CAP) flags |= DEMI_V_QUEUE_OVF;
+            K1_SITE(6);
+            if (K1_RARE(n_tq + n_resend > DEMI_TQ_CAP)) { K1_SITE(7); flags |= DEMI_V_QUEUE_OVF; }
             else { tq.append(n_tq, resend); n_tq += n_resend; if (INQ) inq |= just; }     // (every member of resend has its bit in `just`)
           }
           resend.clear(); n_resend = 0; just = 0;
@@ -1171,6 +1227,7 @@ __global__ K1_LAUNCH_BOUNDS void k1_random_explore(const typename K1ArgsOf<V>::t
         if (!deliver) ph = PH_FINISH;
       } else {
         // quiescence: notify_quiescence (:487-500) / handle_quiescence (ExternalEventInjector.scala:541-580)
+        K1_SITE(11);
         if ((flags & DEMI_OVF_ANY) || viol || tidx >= E) {
           ph = PH_FINISH;
         } else {
@@ -1310,7 +1367,8 @@ __global__ K1_LAUNCH_BOUNDS void k1_random_explore(const typename K1ArgsOf<V>::t
       // handle_timer_cancel: messagesToSend first - the first of its n_tq entries for this timer (TimerQ::remove_first), looked
       // for only when the timer may be there (`inq` above)
       bool found = false;
-      if (INQ ? (inq & tbit) != 0 : n_tq != 0) {
+      if (INQ ? K1_RARE((inq & tbit) != 0) : n_tq != 0) {
+        K1_SITE(9);
         if (tq.remove_first(n_tq, TimerQ::pack(me, type, tix))) { n_tq--; found = true; }
       }
       if (!found) {
@@ -1322,7 +1380,7 @@ __global__ K1_LAUNCH_BOUNDS void k1_random_explore(const typename K1ArgsOf<V>::t
         const uint32_t d = *p;
         if (d != TD_NONE) {
           const word_t wantw = msg_word(type, DL, me, 0, 0);
-          if (d != TD_MANY) {
+          if (!K1_RARE(d == TD_MANY)) {
 #ifdef DEMI_K1_NO_RM_KNOWN
             pend_remove(d, wantw, LASTW());
 #else
@@ -1332,6 +1390,7 @@ __global__ K1_LAUNCH_BOUNDS void k1_random_explore(const typename K1ArgsOf<V>::t
           } else {
             // several copies were pending at some point: scan.  The scan also counts the copies, so the entry becomes exact
             // again when at most one is left after this removal.
+            K1_SITE(10);
             uint32_t first = 0xFFFFFFFFu, second = 0xFFFFFFFFu, copies = 0;
             for (uint32_t q = 0; q < n_pend; q++)
               if (pend_load(mem, q) == wantw) {
@@ -1440,7 +1499,22 @@ __global__ K1_LAUNCH_BOUNDS void k1_random_explore(const typename K1ArgsOf<V>::t
     }
 
     PH_MARK(9);
+#ifdef DEMI_K1_CENSUS
+    if (!REBIN) {       // (a wave-uniform point: every lane that is still in the loop comes by here)
+      cz_iters++;
+      for (uint32_t s_ = 0; s_ < K1_SITES; s_++) {
+        const uint64_t in_ = __ballot((cz_bits >> s_) & 1u);
+        cz_empty[s_] += in_ == 0;
+        cz_lanes[s_] += (uint32_t)__popcll(in_);
+      }
+      cz_bits = 0;
+    }
+#endif
   }
+#ifdef DEMI_K1_CENSUS
+  if (!REBIN && lane == 0)
+    for (uint32_t s_ = 0; s_ < K1_SITES; s_++) __builtin_printf("K1CENSUS %u %u %u %u\n", s_, cz_empty[s_], cz_lanes[s_], cz_iters);
+#endif
 #ifdef DEMI_K1_PHASES
   PH_MARK(11);
   if (lane == 0 && args.phase_out) {

@@ -64,6 +64,35 @@ __global__ __launch_bounds__(256) void k_probe_mix(unsigned long long* __restric
                      "v_xor_b32 %2, %2, %3\n\ts_add_u32 %6, %6, %7\n\tv_add_u32 %3, %3, %0\n\ts_xor_b32 %7, %7, %4"
                      : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3), "+s"(s0), "+s"(s1), "+s"(s2), "+s"(s3) : : "scc");
     }
+  } else if (kind >= 4) {
+    // what a 32 x 32 multiply costs against an integer add: 64 instructions of ONE opcode per pass on 8
+    // independent accumulators - kind 4 v_add_u32, 5 v_mul_lo_u32, 6 v_mul_hi_u32, 7 v_mad_u64_u32 (four 64-bit accumulators)
+    per_pass = 64;
+    uint32_t a4 = a0 * 11u, a5 = a0 * 13u, a6 = a0 * 17u, a7 = a0 * 19u;
+    unsigned long long b0 = a0, b1 = a1, b2 = a2, b3 = a3, cy;
+    // (one loop per opcode: a test of `kind` inside the loop would sit between the instructions that are being timed)
+#define DEMI_PROBE_OP8(OP)                                                                                                      \
+    for (uint32_t i = 0; i < iters; i++) {                                                                                      \
+      _Pragma("unroll") for (int k = 0; k < 8; k++)                                                                             \
+        asm volatile(OP " %0, %0, %1\n\t" OP " %1, %1, %2\n\t" OP " %2, %2, %3\n\t" OP " %3, %3, %4\n\t"                        \
+                     OP " %4, %4, %5\n\t" OP " %5, %5, %6\n\t" OP " %6, %6, %7\n\t" OP " %7, %7, %0"                              \
+                     : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3), "+v"(a4), "+v"(a5), "+v"(a6), "+v"(a7));                         \
+    }
+    if (kind == 4) { DEMI_PROBE_OP8("v_add_u32") }
+    else if (kind == 5) { DEMI_PROBE_OP8("v_mul_lo_u32") }
+    else if (kind == 6) { DEMI_PROBE_OP8("v_mul_hi_u32") }
+    else {
+      for (uint32_t i = 0; i < iters; i++) {
+#pragma unroll
+        for (int k = 0; k < 8; k++)
+          asm volatile("v_mad_u64_u32 %0, %8, %4, %5, %0\n\tv_mad_u64_u32 %1, %8, %5, %6, %1\n\tv_mad_u64_u32 %2, %8, %6, %7, %2\n\t"
+                       "v_mad_u64_u32 %3, %8, %7, %4, %3\n\tv_mad_u64_u32 %0, %8, %4, %6, %0\n\tv_mad_u64_u32 %1, %8, %5, %7, %1\n\t"
+                       "v_mad_u64_u32 %2, %8, %6, %4, %2\n\tv_mad_u64_u32 %3, %8, %7, %5, %3"
+                       : "+v"(b0), "+v"(b1), "+v"(b2), "+v"(b3), "+v"(a4), "+v"(a5), "+v"(a6), "+v"(a7), "=&s"(cy) : : "vcc");
+      }
+    }
+#undef DEMI_PROBE_OP8
+    a0 ^= a4 ^ a5 ^ a6 ^ a7 ^ (uint32_t)(b0 ^ b1 ^ b2 ^ b3) ^ (uint32_t)((b0 ^ b1 ^ b2 ^ b3) >> 32);
   } else {
     per_pass = 16 * 7;
     for (uint32_t i = 0; i < iters; i++) {

@@ -1416,7 +1416,8 @@ typedef struct {
 int demi_device_probe(demi_ctx* ctx, uint32_t waves_per_simd, uint32_t iters, demi_probe_result* out);
 /* The same for other instruction kinds (cycles_per_valu is then SIMD cycles per instruction of the probe's mix): kind 0 =
  * integer VALU (demi_device_probe), 1 = SALU only, 2 = VALU and SALU alternating, 3 = the code of a divergent two-instruction
- * `if` (saveexec / branch / body / restore).                                                                             */
+ * `if` (saveexec / branch / body / restore); one opcode alone: 4 = v_add_u32, 5 = v_mul_lo_u32, 6 = v_mul_hi_u32,
+ * 7 = v_mad_u64_u32 (what a 32 x 32 multiply costs against an add).                                                      */
 int demi_device_probe_mix(demi_ctx* ctx, uint32_t waves_per_simd, uint32_t iters, uint32_t kind, demi_probe_result* out);
 /* A kernel with a known byte count for calibrating rocprofv3's FETCH_SIZE / WRITE_SIZE: mode 0 writes / 1 reads `bytes`
  * with 4 B per lane (K1's scratch rows), 2 writes / 3 reads with 16 B per lane (the verdict array's pattern).          */
